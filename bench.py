@@ -20,8 +20,13 @@ Other workloads (`--workload`), same JSON contract:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 3 --warmup 1 [--workload C4]
 
-Rank 0 prints ONE compact JSON line (< 6 KB: the driver keeps an 8 KB tail; `--verbose` prints the verbose record instead, which
-is always written to gpurun_out/bench_detail.json).  Beside the contract's keys:
+Rank 0 prints ONE compact JSON line (< 6 KB: the driver keeps an 8 KB tail; `--verbose` prints the verbose record instead).  A plain
+run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, the outputs (`--dump-outputs DIR`) and
+the line with the contract's keys (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, dtype, config).
+
+    python bench.py --gpus 1 --steps 20 --warmup 2 --dump-outputs out/     # + the last timed step's outputs as out/<name>.npy
+
+`--full` adds everything else below (and writes the verbose record to a side file, `write_detail`):
   roofline       the dominant kernel: `achieved` = the bytes the kernel HAS to move per launch (bytes_per_unit x
                  units_per_launch) / launch time, against the 8 TB/s HBM peak (`frac`); `traffic` = the HBM bytes the counters saw
                  per launch; `limiter` / `limiter_frac` = the resource that binds the kernel and how much of it is in use ("valu": share
@@ -35,6 +40,7 @@ is always written to gpurun_out/bench_detail.json).  Beside the contract's keys:
                  C2 run at N = 1 only), one row each (`legs_cols`)
   cpu_baseline   the NumPy oracle timed on the host cores on a bounded sample of the same workload (N = 1, rank 0)
   check          an independent re-evaluation of the result outside the timed region
+  multi_gpu      (N > 1) gather_alone_ms_rank0: one blocking gather after the timed region, nothing else on the chip
   legend         what the figures mean, every string once
 """
 import argparse
@@ -782,6 +788,32 @@ def reference_trace_check(leg):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+DUMP_WAVE_BYTES = 48 << 20          # waveforms beyond this: a fixed, seeded sample of whole items (C2's 64 x 523776 float32 is 134 MB)
+
+
+def dump_outputs(out_dir, leg, x):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64), so that two builds can
+    be compared output for output on the same seeded inputs.  waveform.npy: the (items, length) waveforms - every item, or the items
+    listed in waveform_items.npy (drawn by default_rng(0), sorted) when the whole batch exceeds DUMP_WAVE_BYTES; evals.npy (Griffin-Lim,
+    ADMM): the (iteration, metric in dB, loss) rows of the step's evaluations.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = x.detach()
+    n, row_bytes = x.shape[0], x[0].numel() * x.element_size()
+    arrays = {}
+    if n * row_bytes > DUMP_WAVE_BYTES:
+        k = max(1, DUMP_WAVE_BYTES // row_bytes)
+        items = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        x = x[torch.from_numpy(items).to(x.device)]
+        arrays["waveform_items"] = items.astype(np.float64)
+    arrays["waveform"] = x.cpu().numpy()
+    if leg.state.get("evals") is not None:
+        arrays["evals"] = np.array(leg.state["evals"], dtype=np.float64).reshape(-1, 3)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # The ONE line the driver keeps a tail of: everything a reader needs to recompute the claims, every string once (`legend`), the
 # short legs as rows of one table; the verbose record (every `what` / `formula`, raw counters per leg) goes to a side file.
 LEG_COLS = ["value", "unit", "ms_per_step", "steps", "launch_ms", "roofline_frac_hbm", "traffic_bytes", "limiter", "limiter_frac",
@@ -865,7 +897,8 @@ def compact_line(full):
             out[k] = full[k]
     if full.get("h2d"):
         out["h2d_serial"] = [full["h2d"]["serial"]["value"], full["h2d"]["serial"]["ms_per_step"]]
-    out["roofline"] = _compact_roof(full["roofline"])
+    if full.get("roofline"):
+        out["roofline"] = _compact_roof(full["roofline"])
     if full.get("cpu_baseline"):
         out["cpu_baseline"] = full["cpu_baseline"]
     if full.get("multi_gpu"):
@@ -880,8 +913,9 @@ def compact_line(full):
         out["legs_cols"] = LEG_COLS
         out["legs"] = {k: _leg_row(e) for k, e in legs.items()}
         out["legs_workloads"] = {k: _short_workload(e["workload"]) for k, e in legs.items() if "workload" in e}
-    out["legend"] = LEGEND
-    for k in ("bench_seconds", "detail"):
+    if full.get("roofline"):
+        out["legend"] = LEGEND
+    for k in ("bench_seconds", "outputs", "detail"):
         if k in full:
             out[k] = full[k]
     return _r(out)
@@ -1015,6 +1049,13 @@ def build_parser():
                          "y.s > 1e-10; its default tolerances end most steps after one iteration on this input); 'memory': strong "
                          "Wolfe with both tolerances at 0, so that every step runs its 20 iterations, the memory fills to "
                          "history_size = 100 and the recursion's passes over 200 vectors carry weight - use --outer 8 or more")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: roofline (live rocprofv3 --pmc passes over a child process), self-checks, "
+                         "H2D-inclusive legs, the short legs of the other workloads after the default C2 run, the CPU baseline, the "
+                         "verbose record on disk; the --no-* options below leave parts of it out (default: set-up, warm-up, the timed "
+                         "steps and the result line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the C4 / C3 / C5 legs that follow the default C2 run")
@@ -1032,8 +1073,8 @@ def build_parser():
     ap.add_argument("--keep-pmc", default=None, help="directory to keep the raw per-dispatch counter CSVs of the live passes in")
     ap.add_argument("--generic", action="store_true", help="force the generic (unfused) kernels")
     ap.add_argument("--verbose", action="store_true", help="print the verbose record (every what / formula string, raw counters per "
-                                                           "leg) instead of the compact line; it is always written to "
-                                                           "gpurun_out/bench_detail.json")
+                                                           "leg) instead of the compact line; with --full it is also written to "
+                                                           "a side file (write_detail)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     return ap
 
@@ -1097,9 +1138,9 @@ def main():
         mine = torch.tensor([elapsed_local, leg.gather_wait_s, 1.0], dtype=torch.float64, device=where)
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
-        # one blocking gather after the timed region, nothing else on the chip: what the exchange itself costs
+        # one blocking gather after the timed region, nothing else on the chip: what the exchange itself costs (--full)
         gather_ms = None
-        if method != "L_BFGS":
+        if args.full and method != "L_BFGS":
             from spectrogram_inversion_amd.distributed import gather_waveforms
             xl = leg.state["x"]
             gather_waveforms(xl, dst=0, sizes=[batch] * world)
@@ -1119,6 +1160,7 @@ def main():
     if rank == 0:
         want = (batch * world if method != "L_BFGS" else batch, leg.length)
         assert tuple(x.shape) == want, (tuple(x.shape), want)
+        outputs = dump_outputs(args.dump_outputs, leg, x) if args.dump_outputs else None
 
     if rank == 0:
         path, geo, kernel = leg.kernel_info()
@@ -1149,50 +1191,55 @@ def main():
         }
         if diag:
             out["multi_gpu"] = diag
+        if outputs:
+            out["outputs"] = {"dir": args.dump_outputs, "names": outputs}
         if method == "L_BFGS":
             out["config"]["lbfgs"] = leg.lbfgs_info()
-        leg.freeze()                       # the launch time belongs to the timed region: later legs reuse the event lists
-        primary_state = dict(leg.state)
-        solo = world == 1 and args.batch is None and not args.generic
-        # ---- counters: live passes over a child process (N = 1), else the stored summary
-        want_extra = solo and args.workload == "C2" and not args.no_extra
-        pmc_all, pmc_source = {}, None
-        if solo and not args.no_pmc and args.workload in DOMINANT:
-            wl = [args.workload] + ([w for w in ("C4", "C3", "C5") if want_extra])
-            pmc_all, pmc_source = live_pmc(wl, keep=args.keep_pmc)
-        pmc, stale, sha = pmc_all.get(args.workload), None, None
-        if not pmc:
-            why = pmc_source
-            pmc, sha, stale = stored_pmc(args.workload, generic=(path == "generic"))
-            pmc_source = "stored: profiles/traffic.json (rocprofv3 --pmc summary), not measured in this run" + \
-                         (f" [live passes: {why}]" if why else "")
-        out["roofline"] = leg.roofline(pmc, pmc_source, stale, sha)
-        if not args.no_check:
-            out["check"] = check(leg, x)
-        # ---- the same step with its input staged over PCIe
-        if world == 1 and not args.no_h2d and method != "L_BFGS":
-            h = leg.h2d_legs(max(3, min(args.steps, 10)), 1)
-            if h:
-                out["value_incl_h2d"] = h["pipelined"]["value"]
-                out["ms_per_step_incl_h2d"] = h["pipelined"]["ms_per_step"]
-                out["h2d"] = h
-        leg.state.update(primary_state)
-        if want_extra:
-            del leg
-            from spectrogram_inversion_amd.plan import clear_plan_cache
-            clear_plan_cache()
-            torch.cuda.empty_cache()
-            out["extra"] = {"workloads": run_extra(args, dev, pmc_all, pmc_source),
-                            "what": "short legs of the other BASELINE workloads, run in this process after the headline's timed "
-                                    "region (same timing rules: warm-up, barrier + synchronize on both sides)"}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(method, WORKLOADS[args.workload][2], WORKLOADS[args.workload][3],
-                                               WORKLOADS[args.workload][4],
-                                               WORKLOADS[args.workload][6] if WORKLOADS[args.workload][6] is not None else 0.0)
+        if args.full:
+            # ---- everything beside the headline figure: roofline, checks, H2D legs, the other workloads, CPU baseline
+            leg.freeze()                       # the launch time belongs to the timed region: later legs reuse the event lists
+            primary_state = dict(leg.state)
+            solo = world == 1 and args.batch is None and not args.generic
+            # ---- counters: live passes over a child process (N = 1), else the stored summary
+            want_extra = solo and args.workload == "C2" and not args.no_extra
+            pmc_all, pmc_source = {}, None
+            if solo and not args.no_pmc and args.workload in DOMINANT:
+                wl = [args.workload] + ([w for w in ("C4", "C3", "C5") if want_extra])
+                pmc_all, pmc_source = live_pmc(wl, keep=args.keep_pmc)
+            pmc, stale, sha = pmc_all.get(args.workload), None, None
+            if not pmc:
+                why = pmc_source
+                pmc, sha, stale = stored_pmc(args.workload, generic=(path == "generic"))
+                pmc_source = "stored: profiles/traffic.json (rocprofv3 --pmc summary), not measured in this run" + \
+                             (f" [live passes: {why}]" if why else "")
+            out["roofline"] = leg.roofline(pmc, pmc_source, stale, sha)
+            if not args.no_check:
+                out["check"] = check(leg, x)
+            # ---- the same step with its input staged over PCIe
+            if world == 1 and not args.no_h2d and method != "L_BFGS":
+                h = leg.h2d_legs(max(3, min(args.steps, 10)), 1)
+                if h:
+                    out["value_incl_h2d"] = h["pipelined"]["value"]
+                    out["ms_per_step_incl_h2d"] = h["pipelined"]["ms_per_step"]
+                    out["h2d"] = h
+            leg.state.update(primary_state)
+            if want_extra:
+                del leg
+                from spectrogram_inversion_amd.plan import clear_plan_cache
+                clear_plan_cache()
+                torch.cuda.empty_cache()
+                out["extra"] = {"workloads": run_extra(args, dev, pmc_all, pmc_source),
+                                "what": "short legs of the other BASELINE workloads, run in this process after the headline's timed "
+                                        "region (same timing rules: warm-up, barrier + synchronize on both sides)"}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(method, WORKLOADS[args.workload][2], WORKLOADS[args.workload][3],
+                                                   WORKLOADS[args.workload][4],
+                                                   WORKLOADS[args.workload][6] if WORKLOADS[args.workload][6] is not None else 0.0)
         out["bench_seconds"] = time.perf_counter() - t_begin
-        detail = write_detail(out)
-        if detail:
-            out["detail"] = detail
+        if args.full:
+            detail = write_detail(out)
+            if detail:
+                out["detail"] = detail
         print(json.dumps(out if args.verbose else compact_line(out)), flush=True)
     if world > 1:
         dist.barrier()

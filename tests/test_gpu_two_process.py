@@ -111,7 +111,7 @@ def test_bench_world_size_two_rehearsal(workload, extra):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", workload, "--no-cpu-baseline"] + extra
+           "--workload", workload, "--no-cpu-baseline", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=800)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -126,3 +126,38 @@ def test_bench_world_size_two_rehearsal(workload, extra):
         assert mg["gather"].startswith("blocking" if "--no-overlap-gather" in extra else "overlapped")
     else:
         assert d["config"]["parallelism"].startswith("replicas x2")
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_what_it_computed(tmp_path):
+    """A plain `bench.py` run (no `--full`): the timed steps and the contract's keys, nothing of --full's; `--dump-outputs` writes
+    the last timed step's waveform and evaluations - the same on a second run, and what this process computes from the same
+    seeded input (C1: rank 0's magnitudes, 50 iterations at alpha 0, an evaluation every 10)."""
+    import json
+    import subprocess
+    from spectrogram_inversion_amd.plan import args_helper, get_plan
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "C1"]
+    runs = []
+    for d in ("a", "b"):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert not {"roofline", "check", "legs", "cpu_baseline", "value_incl_h2d", "detail"} & set(d)
+    assert d["outputs"]["names"] == ["evals", "waveform"]
+    w = [np.load(tmp_path / r / "waveform.npy") for r in ("a", "b")]
+    ev = [np.load(tmp_path / r / "evals.npy") for r in ("a", "b")]
+    assert w[0].dtype == np.float32 and w[0].shape == (1, 511 * 256) and ev[0].dtype == np.float64 and ev[0].shape == (5, 3)
+    assert ev[0][:, 0].tolist() == [9, 19, 29, 39, 49]                       # (0-based: the last iteration of every ten)
+    dev = torch.device("cuda", 0)
+    mag = torch.from_numpy(np.random.default_rng(1234).random((1, 513, 512), dtype=np.float32)).to(dev)
+    plan = get_plan(args_helper(mag, hop_length=256, window=torch.from_numpy(hann(1024))), 1, 512, torch.float32, dev)
+    plan.gla_init(None, mag, 0.0)
+    _, evals = plan.run(50, 10, 0.0, "sc")
+    x = plan.wave().cpu().numpy()
+    for wi, ei in zip(w, ev):
+        assert np.linalg.norm(wi - x) <= 1e-5 * np.linalg.norm(x)
+        np.testing.assert_allclose(ei, np.array(evals), rtol=1e-5)

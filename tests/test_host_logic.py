@@ -365,3 +365,31 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"] and "--nproc-per-node" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "4"
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "4", "--steps", "3", "--workload", "C4"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py` runs lean unless `--full`; `--dump-outputs DIR` writes the last step's waveforms (every item, or a fixed sample of
+    whole items past DUMP_WAVE_BYTES, listed in waveform_items) and its evaluations as float32 / float64 .npy files."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.build_parser().parse_args(["--steps", "3"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    assert bench.build_parser().parse_args(["--full", "--dump-outputs", "d"]).dump_outputs == "d"
+    x = torch.arange(64 * 1024, dtype=torch.float32).reshape(64, 1024)
+    leg = types.SimpleNamespace(state={"evals": [(10, -20.5, 0.25), (20, -30.0, 0.125)]})
+    assert bench.dump_outputs(str(tmp_path / "all"), leg, x) == ["evals", "waveform"]
+    w = np.load(tmp_path / "all" / "waveform.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, x.numpy())
+    ev = np.load(tmp_path / "all" / "evals.npy")
+    assert ev.dtype == np.float64 and ev.tolist() == [[10, -20.5, 0.25], [20, -30.0, 0.125]]
+    monkeypatch.setattr(bench, "DUMP_WAVE_BYTES", 10 * 4096)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), types.SimpleNamespace(state={}), x.double()) == ["waveform", "waveform_items"]
+    items = np.load(tmp_path / "s1" / "waveform_items.npy")
+    w = np.load(tmp_path / "s1" / "waveform.npy")
+    assert items.dtype == np.float64 and len(items) == 5 and np.all(np.diff(items) > 0)
+    assert w.dtype == np.float64 and np.array_equal(w, x.double().numpy()[items.astype(int)])
+    assert np.array_equal(items, np.load(tmp_path / "s2" / "waveform_items.npy"))

@@ -17,7 +17,7 @@ for rnd in range(int(os.environ.get("AB_ROUNDS", "3"))):
         env = dict(os.environ, SPECINV_LIB=os.path.abspath(path))
         for kv in filter(None, extra.split(",")):
             env[kv.split("=")[0]] = kv.split("=")[1]
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-pmc", "--no-cpu-baseline", "--no-h2d",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extra", "--no-pmc", "--no-cpu-baseline", "--no-h2d",
                               "--no-check", *args], env=env, capture_output=True, text=True)
         try:
             d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
