@@ -222,6 +222,24 @@ int specinv_rtisi_stream_push(specinv_plan* plan, const void* mag, int k, void* 
                               int64_t* n_out);
 int specinv_rtisi_stream_flush(specinv_plan* plan, void* x_out, int64_t out_stride, int64_t* n_out);
 
+/* ---- Mel-spectrogram inversion, first stage: the linear magnitude (librosa's mel_to_stft) -------
+ * Not in the reference, whose recipe for a mel spectrogram is L_BFGS on a log-mel transform (its README).  Per frame
+ * (item b, frame t) with M the (n_mels, F) filterbank and y the mel column:
+ *     minimise 1/2 |M s - y|^2 subject to s >= 0
+ * by FISTA from s = 0, n_iter iterations of step 1 / lipschitz (z = s = 0, t = 1; g = M^T (M z - y),
+ * s' = max(0, z - g / L), t' = (1 + sqrt(1 + 4 t^2)) / 2, z = s' + ((t - 1) / t') (s' - s)), then s ** (1 / power).
+ * One launch runs every iteration of every frame.
+ * `setup` takes the filterbank (a device array of the plan's dtype, F = specinv_plan_n_freq columns) and its constant
+ * lipschitz = lambda_max(M M^T) (the host computes it, in float64); any matrix is valid, a sparse (banded) one is fast.
+ * The plan keeps what it built until the next setup or its destruction.  EINVAL: n_mels <= 0, lipschitz <= 0 or not finite,
+ * mel_fb NULL; EUNSUPPORTED: more than 32767 bands. */
+int specinv_mel_nnls_setup(specinv_plan* plan, const void* mel_fb, int n_mels, double lipschitz);
+/* mel (B, n_mels, T) -> mag_out (B, F, T), the plan's batch and frames, on its stream.  `power` is the exponent the mel was
+ * built with (mel = M |S|^power: 1 magnitude, 2 power).  n_iter = 0 gives zeros; all-zero frames give exact zeros; negative
+ * mel entries are valid.  EINVAL: n_iter < 0, power <= 0 or not finite, NULL pointers, no setup on this plan (all checked
+ * before anything is enqueued); EUNSUPPORTED: a frame that does not fit a CU's LDS (beyond n_fft 8192 in float64). */
+int specinv_mel_nnls(specinv_plan* plan, const void* mel, int n_iter, double power, void* mag_out);
+
 /* ---- L_BFGS building blocks (methods.py:509-569 + torch.optim.LBFGS) -------------------- */
 /* transform kinds for the fused forward/backward: V = |STFT(x)| or V = log1p(M |STFT(x)|) */
 enum { SPECINV_TF_MAG = 0, SPECINV_TF_LOGMEL = 1 };

@@ -121,6 +121,8 @@ SIGNATURES = {
     "specinv_lbfgs_stats_dev": (C.c_int, [_P, _P, _P, _I64, _P]),
     "specinv_lbfgs_pair_stats_dev": (C.c_int, [_P, _P, _P, _P, _D, _P, _P, _I64, _P]),
     "specinv_read_doubles": (C.c_int, [_P, _P, C.c_int, _DP]),
+    "specinv_mel_nnls_setup": (C.c_int, [_P, _P, C.c_int, _D]),
+    "specinv_mel_nnls": (C.c_int, [_P, _P, C.c_int, _D, _P]),
 }
 
 _lib = None

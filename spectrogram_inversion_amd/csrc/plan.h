@@ -9,6 +9,12 @@ namespace specinv {
 
 enum class Method { None, Gla, Admm };
 
+// the mel-inversion state of a plan (specinv_mel_nnls_setup; tu_mel_nnls.hip owns its layout)
+struct MelNnlsState;
+struct MelNnlsFree {
+  void operator()(MelNnlsState* st) const;
+};
+
 // Type-erased interface; PlanT<float> / PlanT<double> implement it (plan_impl.h).
 struct PlanBase {
   specinv_stft_cfg cfg{};
@@ -23,6 +29,7 @@ struct PlanBase {
   bool keep_latched = false; // ... as gla_init / admm_init found it: where the flag selects the kernels (two-sided float32) a run keeps them
   int64_t dev_bytes = 0;   // device memory held by the plan's buffers (account_bytes)
   int objective_kind = -1;   // what the last transform_loss_grad ran (specinv_transform_objective_kind)
+  std::unique_ptr<MelNnlsState, MelNnlsFree> mel_nnls;   // filterbank in band form + momentum table (specinv_mel_nnls_setup)
 
   virtual ~PlanBase() = default;
   virtual int setup() = 0;

@@ -4,6 +4,7 @@
 #include <new>
 #include <vector>
 
+#include "kernels_mel_nnls.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -356,6 +357,25 @@ int specinv_rtisi_stream_push(specinv_plan* plan, const void* mag, int k, void* 
 int specinv_rtisi_stream_flush(specinv_plan* plan, void* x_out, int64_t out_stride, int64_t* n_out) {
   ENTER(plan);
   return plan->impl->rtisi_stream_flush(x_out, out_stride, n_out);
+}
+
+// (the scalar arguments are checked ahead of the plan: their messages need no GPU)
+int specinv_mel_nnls_setup(specinv_plan* plan, const void* mel_fb, int n_mels, double lipschitz) {
+  SI_CHECK(n_mels > 0, SPECINV_EINVAL, "mel_nnls_setup: n_mels must be > 0 (got %d)", n_mels);
+  SI_CHECK(std::isfinite(lipschitz) && lipschitz > 0, SPECINV_EINVAL, "mel_nnls_setup: lipschitz must be finite and > 0 (got %g)",
+           lipschitz);
+  SI_CHECK(mel_fb != nullptr, SPECINV_EINVAL, "mel_nnls_setup: mel_fb is NULL");
+  ENTER(plan);
+  return mel_nnls_setup(*plan->impl, mel_fb, n_mels, lipschitz);
+}
+int specinv_mel_nnls(specinv_plan* plan, const void* mel, int n_iter, double power, void* mag_out) {
+  SI_CHECK(n_iter >= 0, SPECINV_EINVAL, "mel_nnls: n_iter must be >= 0 (got %d)", n_iter);
+  SI_CHECK(std::isfinite(power) && power > 0, SPECINV_EINVAL, "mel_nnls: power must be finite and > 0 (got %g)", power);
+  SI_CHECK(mel != nullptr && mag_out != nullptr, SPECINV_EINVAL, "mel_nnls: mel / mag_out is NULL");
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->mel_nnls != nullptr, SPECINV_EINVAL, "mel_nnls: specinv_mel_nnls_setup has not been called on this plan");
+  ENTER(plan);
+  return mel_nnls_run(*plan->impl, mel, n_iter, power, mag_out);
 }
 
 int specinv_transform_setup(specinv_plan* plan, int kind, const void* mel_fb, int n_mels) {
