@@ -31,7 +31,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libspecinv.so")
 ARCH = "gfx950"
 BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
               # the SLP vectoriser's packing choices cost registers in the wave-level FFT kernels: measured on one box,
-              # without it k_fused4 0.312 vs 0.318 ms, 2048/256 and 512/128 +10 %, RTISI-LA +14 % (tools/ab_generic.sh)
+              # without it k_fused4 0.312 vs 0.318 ms, 2048/256 and 512/128 +10 %, RTISI-LA +14 %
               "-fno-slp-vectorize"]
 
 

@@ -85,7 +85,7 @@ __device__ inline double si_hypot(double a, double b) { return hypot(a, b); }
 
 // 1 / (|s| + 1e-16), the factor of the reference's projection (methods.py:246-247, :472: s m / (|s| + 1e-16) - ATen multiplies by
 // the rounded reciprocal), without the library's hypot and an IEEE division (~45 / ~60 instructions per bin):
-//   float32: the wave-level kernels' chain (fast_core.h: ref_rcp_abs, SPECINV_REFCHAIN 2) - t = |s|^2 + 1e-32 by two fma, y =
+//   float32: the wave-level kernels' chain (fast_core.h: ref_rcp_abs) - t = |s|^2 + 1e-32 by two fma, y =
 //     v_rsq_f32(t), one Newton step to the correctly rounded t^-1/2; the guard is below float32's resolution above |s| = 3e-9;
 //     below that, and where |s|^2 leaves float32's range, hypot and the division (the float64 overload's rule);
 //   float64: y = v_rsq_f64(t) refined twice, h = t y corrected to the rounded square root, + 1e-16 (visible in float64: 1e-13

@@ -38,47 +38,9 @@
 #include "common.h"
 #include "kernels_generic.h"
 
-// build-time tunables of the fused kernel (tools/sweep_variants.py builds variants, tools/run_variants.sh times them)
-#ifndef SPECINV_XPREF      // 0: load the frame when it starts; 1: carry the samples in registers and prefetch one
-#define SPECINV_XPREF 1    //    hop-block ahead (measured best: 0.336 vs 0.352 ms on C2); 2: fetch the whole next
-#endif                     //    frame after the spectral update so that it flies during the inverse FFT
-#ifndef SPECINV_PLATE      // 0: issue the state loads at the start of the frame; 1: after the forward FFT;
-#define SPECINV_PLATE 0    // 2: one frame ahead, right after the previous frame's spectral update freed the registers
-#endif
-#ifndef SPECINV_TW_REGS    // 1: keep the pass-1 twiddles of the FFT in registers instead of re-reading the LDS table
-#define SPECINV_TW_REGS 1   // measured on C2: 0.313 vs 0.318 ms
-#endif
-#ifndef SPECINV_ABLATE     // timing experiments (WRONG RESULTS): 1 no state stores, 2 no state loads, 4 no FFTs
-#define SPECINV_ABLATE 0
-#endif
-#ifndef SPECINV_MINWAVES   // __launch_bounds__ waves per SIMD (caps the register allocation)
-#define SPECINV_MINWAVES 2
-#endif
-#ifndef SPECINV_PRIO        // k_fused4: wave priority (bits 0-1) while a frame's state loads and the sample prefetch are being
-#define SPECINV_PRIO 1      // issued, so that they are not queued behind the other wave's FFT; +4: also around the output
-#endif                      // store.  Measured on two boxes (C2, ms per launch): 0 0.3023 / 0.3093, 1 0.2997, 3 0.3011 / 0.3042
-#ifndef SPECINV_WGW         // most waves per workgroup of k_fused4 (they share the window / twiddle tables in LDS): 8-wave
-#define SPECINV_WGW 8       // workgroups (one per CU) measured 2-3 % faster than 4-wave ones once every wave slot is filled
-#endif
-#ifndef SPECINV_NT
-#define SPECINV_NT 1         // nontemporal state streams (keeps the re-used samples in L2)
-#endif
 #ifndef SPECINV_IEEE        // 1 (default): the reference's operation order in the projection, (s m) r with r the correctly rounded
 #define SPECINV_IEEE 1      //    1 / |s|, and a true division by the envelope (methods.py:132,246-247; ref_rcp_abs2 below);
 #endif                      // 0: s (m v_rsq_f32(|s|^2 + 1e-32)) and a multiplication by 1 / envelope (the fast_approx copy)
-
-#ifndef SPECINV_REFCHAIN    // (experiments) 1: RN(1 / (RN(sqrt t) + 1e-16)), both roundings; 2: one Newton step to RN(t^-1/2)
-#define SPECINV_REFCHAIN 2
-#endif
-#ifndef SPECINV_REFBREADTH  // (experiments) 1: the chain written breadth-first over a frame's pairs in k_fused_td
-#define SPECINV_REFBREADTH 1
-#endif
-#ifndef SPECINV_K4_ENVREG
-#define SPECINV_K4_ENVREG 1
-#endif
-#ifndef SPECINV_R8_W3        // n_fft 1024: three waves per SIMD (3072 wave slots; 12-wave workgroups at hop 256).  The plain launches fit
-#define SPECINV_R8_W3 1      // 168 registers (ADMM 2 spilled, the evaluating variants 8-31); measured against two waves per SIMD:
-#endif                       // C4 34.3 -> 32.3 ms per step, Griffin-Lim 1024 / 256 0.135 -> 0.127 ms per iteration
 
 // The wave-level kernels are compiled twice: as `specinv::fast` with the reference's operation order and correctly rounded factors
 // (SPECINV_IEEE=1, the default arithmetic since round 4: + 3 % on the headline step, tools/refchain_study.py), and - in the
@@ -93,6 +55,13 @@
 namespace specinv {
 namespace SI_FAST_NS {
 
+// Launch shapes that the kernels' __launch_bounds__ and the host's launch setup (fast_state.h) agree on (tools/log/EXPERIMENTS.md)
+constexpr int kMinWaves = 2;       // waves per SIMD of the wave-level kernels (caps the register allocation)
+constexpr int kFused4Waves = 8;    // most waves per workgroup of k_fused4 / k_fused4_td: one 8-wave workgroup per CU measured 2-3 %
+                                   // faster than 4-wave ones once every wave slot is filled
+constexpr int kR8Waves = 3;        // ... at n_fft 1024 (R = 8): three waves per SIMD, 12-wave workgroups (168 registers; against two:
+                                   // C4 34.3 -> 32.3 ms per step, Griffin-Lim 1024 / 256 0.135 -> 0.127 ms per iteration)
+
 using v2f = float __attribute__((ext_vector_type(2)));
 using v4f = float __attribute__((ext_vector_type(4)));
 
@@ -104,31 +73,20 @@ __device__ __forceinline__ v2f cmulc_k(v2f a, v2f b) { return v2f{a.x * b.x + a.
 // ... with both operands in registers: TWO packed operations - the VOP3P source modifiers broadcast a.x / a.y over both
 // halves, pick b's halves crosswise and negate one product (the compiler emits 2 v_mul + 2 v_fma for the scalar form; the
 // wave-level kernels are bound by the instructions a wave can issue, a packed one counts once)
-#ifndef SPECINV_ASM_CMUL
-#define SPECINV_ASM_CMUL 1
-#endif
 __device__ __forceinline__ v2f cmul(v2f a, v2f b) {
-#if SPECINV_ASM_CMUL
   v2f t, d;   // (one asm statement: between two the compiler puts an s_nop, which costs an issue slot)
   asm("v_pk_mul_f32 %1, %2, %3 op_sel:[0,0] op_sel_hi:[0,1]\n\t"                                         // (a.x b.x, a.x b.y)
       "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]"                       // (- a.y b.y, + a.y b.x)
       : "=v"(d), "=&v"(t) : "v"(a), "v"(b));
   return d;
-#else
-  return cmul_k(a, b);
-#endif
 }
 // a * conj(b)
 __device__ __forceinline__ v2f cmulc(v2f a, v2f b) {
-#if SPECINV_ASM_CMUL
   v2f t, d;
   asm("v_pk_mul_f32 %1, %2, %3 op_sel:[0,0] op_sel_hi:[0,1] neg_hi:[1,0]\n\t"                             // (a.x b.x, - a.x b.y)
       "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]"                                      // (+ a.y b.y, + a.y b.x)
       : "=v"(d), "=&v"(t) : "v"(a), "v"(b));
   return d;
-#else
-  return cmulc_k(a, b);
-#endif
 }
 __device__ __forceinline__ v2f cconj(v2f a) { return v2f{a.x, -a.y}; }
 __device__ __forceinline__ v2f mul_i(v2f a) { return v2f{-a.y, a.x}; }    // a * (+i)
@@ -138,7 +96,6 @@ __device__ __forceinline__ v2f mul_mi(v2f a) { return v2f{a.y, -a.x}; }   // a *
 // assembly and would leave each pair back to back)
 template <bool CONJ>
 __device__ __forceinline__ void cmul_x4(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v2f b0, v2f b1, v2f b2, v2f b3) {
-#if SPECINV_ASM_CMUL
   v2f t0, t1, t2, t3;
   if (!CONJ) {
     asm("v_pk_mul_f32 %4, %0, %8 op_sel:[0,0] op_sel_hi:[0,1]\n\t"
@@ -163,12 +120,6 @@ __device__ __forceinline__ void cmul_x4(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v2f 
         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
         : "v"(b0), "v"(b1), "v"(b2), "v"(b3));
   }
-#else
-  a0 = CONJ ? cmulc_k(a0, b0) : cmul_k(a0, b0);
-  a1 = CONJ ? cmulc_k(a1, b1) : cmul_k(a1, b1);
-  a2 = CONJ ? cmulc_k(a2, b2) : cmul_k(a2, b2);
-  a3 = CONJ ? cmulc_k(a3, b3) : cmul_k(a3, b3);
-#endif
 }
 // z[i] <- z[i] * w(i) for i = FIRST .. R-1 (R a multiple of 4, FIRST 0 or 1)
 template <int R, bool PK, bool CONJ, int FIRST, typename W>
@@ -193,15 +144,11 @@ template <bool PK>
 __device__ __forceinline__ v2f cmulc_p(v2f a, v2f b) { return PK ? cmulc(a, b) : cmulc_k(a, b); }
 // (-i w) * d = (w.y d.x + w.x d.y, w.y d.y - w.x d.x) without forming -i w
 __device__ __forceinline__ v2f cmul_mi(v2f w, v2f d) {
-#if SPECINV_ASM_CMUL
   v2f t, r;
   asm("v_pk_mul_f32 %1, %2, %3 op_sel:[1,0] op_sel_hi:[1,1]\n\t"                                         // (w.y d.x, w.y d.y)
       "v_pk_fma_f32 %0, %2, %3, %1 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]"                       // (+ w.x d.y, - w.x d.x)
       : "=v"(r), "=&v"(t) : "v"(w), "v"(d));
   return r;
-#else
-  return cmul_k(v2f{w.y, -w.x}, d);
-#endif
 }
 template <bool INV>
 __device__ __forceinline__ v2f rot(v2f a) { return INV ? mul_i(a) : mul_mi(a); }
@@ -214,9 +161,6 @@ __device__ __forceinline__ v2f dirmul(v2f a, v2f w) { return INV ? cmulc_k(a, w)
 // packed operations like cmul (VOP3P takes no literal, but one scalar source) instead of the four scalar ones with inline
 // literals; the in-register DFTs' fixed twiddles and the W_64^j steps of the real-FFT split are 43 such products per frame
 // and iteration at n_fft 2048 (86 of ~1240 vector instructions)
-#ifndef SPECINV_PKCONST
-#define SPECINV_PKCONST 1
-#endif
 template <bool INV>
 __device__ __forceinline__ v2f cmul_sk(v2f a, v2f w) {
   v2f t, d;
@@ -261,7 +205,7 @@ __device__ __forceinline__ void cmul_sk_x4(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v
 }
 template <bool INV, bool PK>
 __device__ __forceinline__ void dirmul_x4(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v2f w0, v2f w1, v2f w2, v2f w3) {
-  if (PK && SPECINV_PKCONST) {
+  if (PK) {
     cmul_sk_x4<INV>(a0, a1, a2, a3, w0, w1, w2, w3);
   } else {
     a0 = dirmul<INV>(a0, w0);
@@ -272,7 +216,7 @@ __device__ __forceinline__ void dirmul_x4(v2f& a0, v2f& a1, v2f& a2, v2f& a3, v2
 }
 template <bool INV, bool PK>
 __device__ __forceinline__ v2f dirmul_p(v2f a, v2f w) {
-  if (PK && SPECINV_PKCONST) return cmul_sk<INV>(a, w);
+  if (PK) return cmul_sk<INV>(a, w);
   return dirmul<INV>(a, w);
 }
 
@@ -283,54 +227,31 @@ __device__ __forceinline__ v2f shfl2(v2f a, int src) { return v2f{__shfl(a.x, sr
 
 // a + i*b and a - i*b as ONE packed add: VOP3P source modifiers pick b's halves crosswise (op_sel) and negate
 // one of them, so the multiplication by +-i costs nothing (the compiler otherwise emits v_xor + v_mov for it).
-#ifndef SPECINV_ASM_ROT
-#define SPECINV_ASM_ROT 1
-#endif
 __device__ __forceinline__ v2f add_i(v2f a, v2f b) {   // (a.x - b.y, a.y + b.x)
-#if SPECINV_ASM_ROT
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
-#else
-  return v2f{a.x - b.y, a.y + b.x};
-#endif
 }
 __device__ __forceinline__ v2f sub_i(v2f a, v2f b) {   // (a.x + b.y, a.y - b.x)
-#if SPECINV_ASM_ROT
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
-#else
-  return v2f{a.x + b.y, a.y - b.x};
-#endif
 }
 
 __device__ __forceinline__ v2f add_conj(v2f a, v2f b) {   // a + conj(b)
-#if SPECINV_ASM_ROT
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
-#else
-  return v2f{a.x + b.x, a.y - b.y};
-#endif
 }
 __device__ __forceinline__ v2f sub_conj(v2f a, v2f b) {   // a - conj(b)
-#if SPECINV_ASM_ROT
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
-#else
-  return v2f{a.x - b.x, a.y + b.y};
-#endif
 }
 __device__ __forceinline__ v2f conj_sub_i(v2f a, v2f b) {   // conj(a - i*b) = (a.x + b.y, -a.y + b.x)
-#if SPECINV_ASM_ROT
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
   return d;
-#else
-  return v2f{a.x + b.y, b.x - a.y};
-#endif
 }
 
 // ---- small in-register DFTs (natural order in, natural order out) ------------------------------
@@ -597,9 +518,6 @@ __device__ __forceinline__ void xlane_dft4_out(v2f& A, v2f& B, v2f& C, v2f& D) {
   swap32(A, B);
   swap32(C, D);
 }
-#ifndef SPECINV_XLANE_HALF
-#define SPECINV_XLANE_HALF 1
-#endif
 
 // DFT over lane bit 5 of two registers at once: after the first swap the low half of the wave holds both halves
 // of A (in A, B) and the high half both halves of B
@@ -660,7 +578,7 @@ __device__ __forceinline__ void fft_forward_t(v2f (&z)[R], const LaneConst<R>& k
   if (G::C == 2) {
 #pragma unroll
     for (int g = 0; g < R; g += 2) xlane_dft2(z[g], z[g + 1]);
-  } else if (G::C == 4 && SPECINV_XLANE_HALF && PK) {
+  } else if (G::C == 4 && PK) {
     // slot (A, C, B, D) = (z[g], z[g+2], z[g+1], z[g+3]) holds digit s = 0..3 of the register g + q' this row owns
     // (q' = (0, 2, 1, 3)[lane / 16]): post-twiddle W_64^(n2 s), scratch row s R + g + q'
 #pragma unroll
@@ -724,7 +642,7 @@ __device__ __forceinline__ void fft_inverse_t(v2f (&z)[R], const LaneConst<R>& k
   Dft<R, true, PKC>::run(z);
 #pragma unroll
   for (int i = 0; i < R; ++i) tr[k.tr_b + i] = z[i];
-  if (G::C == 4 && SPECINV_XLANE_HALF && PK) {
+  if (G::C == 4 && PK) {
     // (the mirror image of the forward transform's short cut: the row that owns register g + lane / 16 reads its four row values)
 #pragma unroll
     for (int g = 0; g < R; g += 4) {
@@ -809,7 +727,6 @@ struct FastArgs {
   float* x2_out;
   float tds;            //              (-lr)^t
   int skew;             // chunk_begin's skew (0: even chunks)
-  unsigned long long* stamps;   // SPECINV_TD_STAMPS builds only: [n_waves][8]
   float coef;       // lr (GLA) or rho (ADMM)
   float inv1p;      // 1/(1+rho)
   float fwd_scale;  // 1 or N^-1/2
@@ -831,47 +748,28 @@ __device__ __forceinline__ float fast_rcp(float v) { return __builtin_amdgcn_rcp
 // value on 2^22 random bins, tools/ref_ops_probe.py): abs = hypotf (correctly rounded), and the complex / real division is a
 // multiplication by the rounded RECIPROCAL of the real divisor (c10::complex<T>::operator/= with a zero imaginary part):
 //     out = (s * m) * r,   r = RN(1 / (RN(|s|) + 1e-16)).
-// Here t = |s|^2 by two fused multiply-adds, y = v_rsq_f32(t) (1 ulp), and
-//   SPECINV_REFCHAIN == 2 (shipped): ONE Newton step on y gives r = RN(t^-1/2), the correctly rounded 1 / |s| in all but ~1e-6 of
-//     the cases (one rounding of the exact value where the reference rounds |s| and then its reciprocal): two transcendental and
-//     four packed instructions per PAIR of bins, no division; 73 % of the outputs bit-identical to the reference's chain, rms
-//     deviation from it 4.9e-8 relative - and from the EXACT value 4.7e-8, where the reference's own chain has 5.1e-8;
-//   SPECINV_REFCHAIN == 1: h = t y corrected by one residual step to RN(sqrt t), + 1e-16, one Newton step from y to
-//     RN(1 / (h + 1e-16)): both of the reference's roundings, 88 % bit-identical (the rest is hypotf rounding the exact sum of
-//     squares), three more packed instructions per pair: + 5.3 % on the BASELINE C2 step against + 3.1 % (tools/refchain_study.py,
-//     profiles/r04_refchain.txt).
+// Here t = |s|^2 by two fused multiply-adds, y = v_rsq_f32(t) (1 ulp), and ONE Newton step on y gives r = RN(t^-1/2), the
+// correctly rounded 1 / |s| in all but ~1e-6 of the cases (one rounding of the exact value where the reference rounds |s| and then
+// its reciprocal): two transcendental and four packed instructions per PAIR of bins, no division; 73 % of the outputs bit-identical
+// to the reference's chain, rms deviation from it 4.9e-8 relative - and from the EXACT value 4.7e-8, where the reference's own
+// chain has 5.1e-8.  A chain with both of the reference's roundings (88 % bit-identical) cost + 5.3 % on the BASELINE C2 step
+// against + 3.1 % (tools/refchain_study.py, profiles/r04_refchain.txt).
 // For comparison: the IEEE sqrt + two divisions of rounds 2-3 (x m / d: not the reference's chain) matched 65 % at + 27 %, the
 // approximate path (SPECINV_IEEE=0: s (m rsq(t))) 52 %; every form sits 4.7-5.3e-8 from the exact value.
 // kRefFloor keeps rsq finite at s = 0 (then out = 0 like the reference's 0 / 1e-16) and bounds r by 1e16 like the guard does; it
-// is absorbed by t above |s| = 6e-13 (REFCHAIN 2 has no other guard: it only differs from the reference's below |s| = 3e-9).
+// is absorbed by t above |s| = 6e-13 (the chain has no other guard: it only differs from the reference's below |s| = 3e-9).
 constexpr float kRefFloor = 1e-32f;
 __device__ __forceinline__ float ref_norm2(v2f s, float floor_ = kRefFloor) { return fmaf(s.y, s.y, fmaf(s.x, s.x, floor_)); }
 __device__ __forceinline__ v2f ref_rcp_abs2(v2f t, float guard = 1e-16f) {
   const v2f y = v2f{__builtin_amdgcn_rsqf(t.x), __builtin_amdgcn_rsqf(t.y)};
   v2f h = t * y;
-#if SPECINV_REFCHAIN == 1
-  const v2f res = __builtin_elementwise_fma(-h, h, t);
-  h = __builtin_elementwise_fma(res, y * 0.5f, h);
-  const v2f den = h + guard;
-  const v2f e = __builtin_elementwise_fma(-den, y, v2f{1.0f, 1.0f});
-  return __builtin_elementwise_fma(e, y, y);
-#else
   const v2f e = __builtin_elementwise_fma(-h, y, v2f{1.0f, 1.0f});
   return __builtin_elementwise_fma(y * 0.5f, e, y);
-#endif
 }
 __device__ __forceinline__ float ref_rcp_abs(float t, float guard = 1e-16f) {
   const float y = __builtin_amdgcn_rsqf(t);
   float h = t * y;
-#if SPECINV_REFCHAIN == 1
-  const float res = fmaf(-h, h, t);
-  h = fmaf(res, y * 0.5f, h);
-  const float den = h + guard;
-  const float e = fmaf(-den, y, 1.0f);
-  return fmaf(e, y, y);
-#else
   return fmaf(y * 0.5f, fmaf(-h, y, 1.0f), y);
-#endif
 }
 // The envelope division of methods.py:132 (a true float32 division): q = v r, one residual step - correctly rounded when r is the
 // correctly rounded reciprocal of e (`env_rcp`: v_rcp_f32 + one Newton step), which the kernels keep in registers wherever the
@@ -899,9 +797,6 @@ __device__ __forceinline__ float env_apply(float v, float e) { return v * e; }
 // one transcendental instruction instead of two (they cost two issue slots each) and no addition.  v_rsq_f32 is good to 1 ulp like
 // v_sqrt_f32 and v_rcp_f32 each; the guard term only matters below |s| ~ 1e-9, where both forms tend to m * 1e16, and s = 0 gives
 // 0 either way.  The exact-projection build (SPECINV_IEEE) keeps the reference's operations.
-#ifndef SPECINV_RSQ
-#define SPECINV_RSQ 1
-#endif
 __device__ __forceinline__ float proj_rsq(v2f s) { return __builtin_amdgcn_rsqf(fmaf(s.y, s.y, fmaf(s.x, s.x, 1e-32f))); }
 
 // Frequency-domain update of one bin.  `r` is the STFT bin, `p`/`u` the stored state, `m` the target.
@@ -923,11 +818,8 @@ __device__ __forceinline__ v2f update_bin(v2f r, v2f& p, v2f& u, v2f& xs, float 
     p = s;
 #if SPECINV_IEEE
     return ((s * m) * ref_rcp_abs(ref_norm2(s))) * a.inv_scale;
-#elif SPECINV_RSQ
-    return s * ((m * proj_rsq(s)) * a.inv_scale);
 #else
-    const float inv = fast_rcp(fast_abs(s) + 1e-16f) * a.inv_scale;
-    return v2f{(s.x * m) * inv, (s.y * m) * inv};
+    return s * ((m * proj_rsq(s)) * a.inv_scale);
 #endif
   } else {
     // methods.py:467-475 with p = Y of the previous iteration (= fl(X + U), the first operation of :468)
@@ -940,14 +832,11 @@ __device__ __forceinline__ v2f update_bin(v2f r, v2f& p, v2f& u, v2f& xs, float 
 #pragma clang fp contract(off)   // X is rounded before Y = X + U is formed (:473-475): no multiply-add across the two
       xn = (xn * m) * ref_rcp_abs(ref_norm2(xn));
     }
-#elif SPECINV_RSQ
+#else
     {
 #pragma clang fp contract(off)   // X is rounded before Y = X + U is formed (:473-475): no multiply-add across the two
       xn = xn * (m * proj_rsq(xn));
     }
-#else
-    const float inv = fast_rcp(fast_abs(xn) + 1e-16f);
-    xn = v2f{(xn.x * m) * inv, (xn.y * m) * inv};
 #endif
     xs = xn;
     u = un;
@@ -1025,24 +914,10 @@ __device__ __forceinline__ void load_block(const float* __restrict__ xrow, const
 }
 
 __device__ __forceinline__ v4f ld_stream(const v4f* p) {
-#if SPECINV_ABLATE & 2
-  return v4f{1.0f, 0.5f, 0.25f, 2.0f} * (float)(((unsigned long long)p >> 4) & 7);
-#else
-#if SPECINV_NT
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-#endif
 }
 __device__ __forceinline__ void st_stream(v4f* p, v4f v) {
-#if SPECINV_ABLATE & 1
-  if (v.x == 1.2345e30f) __builtin_nontemporal_store(v, p);   // keeps the value alive, (almost) never stores
-#elif SPECINV_NT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 // ---- hop = n_fft/4: the headline shape keeps its own hand-tuned copy of the kernel --------------------------------
@@ -1110,7 +985,7 @@ __device__ __forceinline__ void td_split_raw(v2f zk, v2f zm, v2f wk, v2f& xk, v2
 template <int R, bool PK = true>
 __device__ __forceinline__ v2f pair_twiddle(v2f wn, int j) {
   if (j == 0) return wn;
-  return (PK && SPECINV_PKCONST) ? cmul_sk<false>(wn, w64(j * (32 / R))) : cmul_k(wn, w64(j * (32 / R)));
+  return PK ? cmul_sk<false>(wn, w64(j * (32 / R))) : cmul_k(wn, w64(j * (32 / R)));
 }
 // s * p.x and s * p.y: ONE packed multiplication each (the scalar factor is picked from a register pair by op_sel)
 __device__ __forceinline__ v2f scale_lo(v2f s, v2f p) {
@@ -1187,9 +1062,6 @@ struct SemiArgs {
   int write_x;             // k_hop_td: 0 = x_{t+1} has no reader (only the seam samples, which the tails kernel needs, are stored)
 };
 
-#ifndef SPECINV_HOP_R8_W2     // k_hop at n_fft 1024: 128 registers (2 - 13 spilled), so that two 8-wave workgroups fit a CU like the host's
-#define SPECINV_HOP_R8_W2 1     // 4096 wave slots assume: ADMM 1024 / 160 0.191 -> 0.182 ms, 1024 / 300 0.197 -> 0.184 (k_hop_td fits as it is and
-#endif                          // measured 5 % slower under the same bound)
 struct HopArgs {
   FastArgs f;              // x_in, x_out, P_out (in place), U_out, m_pairs, ..., nchunks, n_waves, L, T, pad_mode, partials
   const float* env;        // (L) reciprocal of the overlap-add envelope
@@ -1223,15 +1095,11 @@ template <int R, bool EARLY, bool EVAL>
 __global__ void k_fused4_td(FastArgs a);
 template <int R, int OV, bool EARLY, bool EVAL>
 __global__ void k_fused_td(FastArgs a);
-#ifndef SPECINV_EVAL_PIECES          // k_eval_td at BASELINE C2 (rocprofv3): 1 piece / 2 waves per SIMD 0.133 ms, 2 / 3 0.122, 4 / 4 with LDS
-#define SPECINV_EVAL_PIECES 2        // twiddles 0.141 (0.129 at 1 piece) - the fused evaluating variant spends 0.16 on the same work
-#endif
-#ifndef SPECINV_EVAL_WAVES
-#define SPECINV_EVAL_WAVES 3
-#endif
-constexpr int kEvalPieces = SPECINV_EVAL_PIECES;     // pieces of a chunk per wave of k_eval_td (kernels_fast_td.h: kEvalSub)
+// k_eval_td at BASELINE C2: 1 piece / 2 waves per SIMD 0.133 ms, 2 / 3 0.122, 4 / 4 with LDS twiddles 0.141
+constexpr int kEvalPieces = 2;     // pieces of a chunk per wave of k_eval_td (kernels_fast_td.h: kEvalSub)
+constexpr int kEvalWaves = 3;      // its waves per SIMD
 template <int R, int OV>
-__global__ __launch_bounds__(256, SPECINV_EVAL_WAVES) void k_eval_td(FastArgs a);   // (bounds on the declaration too: see rtisi_fast_args.h)
+__global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a);   // (bounds on the declaration too: see rtisi_fast_args.h)
 template <int R>
 __global__ void k_fast_stft(FastXformArgs a);
 template <int R>

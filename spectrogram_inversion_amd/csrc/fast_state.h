@@ -92,14 +92,6 @@ struct FastState {
     default: { constexpr int RR = 32; __VA_ARGS__; } break; \
   }
 
-#ifndef SPECINV_TD_SKEW_DEFAULT
-#define SPECINV_TD_SKEW_DEFAULT 10
-#endif
-#ifndef SPECINV_K4_SKEW1            // begin shifts of the second / third chunk of a triple (frames) at BASELINE C4's launch shape
-#define SPECINV_K4_SKEW1 4          // (C4 step, two runs each: "0,0" 30.38 / 30.38 ms, "3,4" 30.29 / 30.26, "4,6" 29.93 / 29.97, "5,8" 30.49 / 30.20,
-#define SPECINV_K4_SKEW2 6          //  "6,9" 30.27 / 30.21, "6,11" 30.78 / 30.68, "8,12" 30.40 / 30.34: the kernel sits on the memory system, the balance buys 1.4 %)
-#endif
-
 template <>
 struct FastState<float> {
   using v2f = fast::v2f;
@@ -184,7 +176,6 @@ struct FastState<float> {
     R = cfg.n_fft / 128;
     semi = false;
     state_in_place = true;     // (same speed as ping-pong buffers, measured; a third less memory)
-    if (const char* e = getenv("SPECINV_STATE_INPLACE")) state_in_place = e[0] != '0';
     use_template = false;
     if (const char* e = getenv("SPECINV_FUSED_TEMPLATE")) use_template = e[0] == '1';
     // fused kernel: hop = n_fft / 2, / 4 or / 8 (whole registers per hop-block), centred, enough frames
@@ -203,9 +194,6 @@ struct FastState<float> {
     const bool small = (long long)cfg.batch * cfg.n_frames < small_below;
     if (!cfg.center || OV == 0 || cfg.n_frames < OV + 2 || pad >= length || small) {
       // any other hop / centring: frame kernel on the wave-level FFT + gather overlap-add (k_semi)
-      if (const char* e = getenv("SPECINV_DISABLE_SEMI")) {
-        if (e[0] == '1') return SPECINV_OK;
-      }
       semi = true;
       hopk = false;
       OV = 0;
@@ -233,7 +221,6 @@ struct FastState<float> {
         const int floor_ch = std::max(8, (cfg.n_fft - 1) / cfg.hop_length + 1);
         // wave slots: one 8-wave workgroup per CU at n_fft 2048 (LDS), two at 1024, three at 512 (registers allow it)
         long long slots = R >= 16 ? 2048 : R == 8 ? 4096 : 6144;
-        if (const char* e = getenv("SPECINV_HOP_SLOTS")) slots = atoll(e);
         int best_nch = 1;
         double best_cost = 1e300;
         for (int nch = 1; nch <= std::max(1, cfg.n_frames / floor_ch); ++nch) {
@@ -265,8 +252,7 @@ struct FastState<float> {
     // reflected edge samples must not fall on split blocks (first / last chunk long enough): chunks of >= 8 (16) frames.
     const int floor_ch = OV == 8 ? 16 : 8;
     long long slots = 1024LL * (R >= 32 ? 1 : R <= 4 ? 3 : 2);
-    if (SPECINV_R8_W3 && R == 8) slots = 3072;
-    if (const char* e = getenv("SPECINV_FUSED_SLOTS")) slots = atoll(e);      // (experiments: wave slots of the chip)
+    if (R == 8) slots = 1024LL * fast::kR8Waves;
     // SPECINV_CU_BUDGET=k: plan the launch for a chip of 256 - k compute units - the chunk count is chosen so that one round of
     // workgroups leaves k CUs free.  For multi-GPU runs whose RCCL gather overlaps the next step's launches: an iteration
     // workgroup takes a whole CU's registers, so RCCL's workgroups can only run beside a launch that does not fill the chip
@@ -292,7 +278,7 @@ struct FastState<float> {
     // The waves of a SIMD do not run at the same speed (begin_t: skewed chunks): where the skew applies - hop = n_fft/4 at n_fft
     // 2048 (chunk pairs) and 1024 (chunk triples) - a chunk count that pairs / triples up is preferred when it costs at most 4 %
     // more frame times than the best one (round 5: B 65 or 100 at T 1024 took 31 / 20 chunks and ran unskewed)
-    if (OV == 4 && (R == 16 || (SPECINV_R8_W3 && R == 8))) {
+    if (OV == 4 && (R == 16 || R == 8)) {
       const int mult = R == 16 ? 2 : 3;
       auto cost_of = [&](int nch) {
         const long long waves = (long long)cfg.batch * nch;
@@ -337,26 +323,22 @@ struct FastState<float> {
     // (the reference-chain build leaves the real-FFT split unscaled, which is exact only for a power-of-two fwd_scale / 2)
     if (exact && pl.cfg.normalized && !hopk) td = false;
     // k_hop_td writes two signals and re-reads z_t where k_hop writes one: at large hops its emission loop overtakes the saved state
-    // traffic.  Measured crossovers (late iterations, 65 536 frames, tools/r02_hop_td2.sh), emission two samples at a time (even hop,
+    // traffic.  Measured crossovers (late iterations, 65 536 frames, tools/log/EXPERIMENTS.md r02 hop_td2), emission two samples at a time (even hop,
     // padding and length) / one at a time: n_fft 2048: wins up to hop 768 (0.350 vs 0.367 ms), loses at 1000 / wins at 333, loses at
     // 601; n_fft 1024: wins everywhere measured (hop 800: 0.195 vs 0.240) / wins at 301; n_fft 512: wins at 300, loses at 400 / wins
     // at 100, loses at 201
     const bool emit_pairs = ((hop | pl.pad) & 1) == 0 && (pl.length & 1) == 0;
     int hop_td_max = emit_pairs ? (RR == 4 ? 320 : RR == 8 ? 1024 : 800) : (RR == 4 ? 128 : RR == 8 ? 448 : 416);
-    if (const char* e = getenv("SPECINV_HOP_TD_MAX")) hop_td_max = atoi(e);          // (experiments)
     if (hopk && hop > hop_td_max) td = false;
-    if (const char* e = getenv("SPECINV_DISABLE_TD")) {      // tests: the spectral-state kernel
-      if (e[0] == '1') td = false;
-    }
     td_t = 0;
     // Skewed chunks.  Two waves share a SIMD and the arbiter serves the OLDER one first whenever both have an instruction ready:
     // at BASELINE C2 the wave in hardware slot 0 ran 0.132 frames per kilotick against its neighbour's 0.077 and finished after
-    // 69 % of the launch (237 k against 337 k ticks on every one of the 1024 SIMDs, tools/td_waves.py); the neighbour ran the last
+    // 69 % of the launch (237 k against 337 k ticks on every one of the 1024 SIMDs); the neighbour ran the last
     // third alone at 0.143 - a SIMD with two waves does 0.209.  Chunks of 42 and 22 frames instead of 32 and 32 let both finish
     // nearly together (late launch 0.172-0.176 -> 0.166-0.168 ms at 8 ... 10 frames of skew, 0.169 / 0.172 at 12 / 14; the
     // evaluating launches and the initial ISTFT like less of it: whole C2 step 20.54 / 20.18 / 20.12 / 20.14 / 20.41 ms at
-    // 0 / 6 / 8 / 10 / 12, tools/log/r03_skewstep.sh; the other overlaps of n_fft 2048 gain 3.5 % (hop 256) and 2 % (hop 1024)
-    // at the same 8, tools/log/r03_skew_ov.sh).  Only for
+    // 0 / 6 / 8 / 10 / 12, tools/log/EXPERIMENTS.md r03 skewstep; the other overlaps of n_fft 2048 gain 3.5 % (hop 256) and 2 % (hop 1024)
+    // at the same 8, r03 skew_ov).  Only for
     // the launch shape this was measured on - the signal-form kernel at two waves per SIMD with exactly as many waves as the
     // chip has slots for them (BASELINE C2 per GPU: 2048).  SPECINV_TD_SKEW overrides (experiments; 0 switches it off).
     // Also tried: s_setprio by frame parity or by time slice so that the two waves take turns (-2...3 %, no better with the skew).
@@ -368,15 +350,19 @@ struct FastState<float> {
     {
       const int len_ch = pl.Tn() / std::max(1, nchunks);
       if (td && !semi && RR == 16 && OV == 4 && n_waves > 1024 && (nchunks & 1) == 0 && len_ch >= 12) {
-        skew = n_waves == 2048 && len_ch == 32 ? SPECINV_TD_SKEW_DEFAULT : std::min((len_ch + 2) / 4, len_ch - 8);
+        constexpr int kSkewC2 = 10;   // frames, at BASELINE C2's launch shape (2048 waves, chunks of 32): measured above
+        skew = n_waves == 2048 && len_ch == 32 ? kSkewC2 : std::min((len_ch + 2) / 4, len_ch - 8);
         if (skew < 2) skew = 0;
       }
       // ... and the n_fft 1024 kernels (spectral state or signal form) at three waves per SIMD (12-wave workgroups, the hardware
       // slot is the wave's index in the workgroup / 4, kernels_fused.h): chunk triples, the oldest wave the longest.  BASELINE
       // C4's shard: 3072 waves, chunks of 64 frames, begin shifts 4 / 6; other chunk lengths scale them.
       if (!semi && RR == 8 && OV == 4 && !use_template && fused_wgw() == 12 && nchunks % 3 == 0 && len_ch >= 16) {
-        const int s1 = len_ch == 64 ? SPECINV_K4_SKEW1 : (SPECINV_K4_SKEW1 * len_ch + 32) / 64;
-        const int s2 = len_ch == 64 ? SPECINV_K4_SKEW2 : (SPECINV_K4_SKEW2 * len_ch + 32) / 64;
+        // (C4 step, two runs each: "0,0" 30.38 / 30.38 ms, "3,4" 30.29 / 30.26, "4,6" 29.93 / 29.97, "5,8" 30.49 / 30.20, "6,9"
+        // 30.27 / 30.21: the kernel sits on the memory system, the balance buys 1.4 %)
+        constexpr int kSkew1 = 4, kSkew2 = 6;
+        const int s1 = len_ch == 64 ? kSkew1 : (kSkew1 * len_ch + 32) / 64;
+        const int s2 = len_ch == 64 ? kSkew2 : (kSkew2 * len_ch + 32) / 64;
         if ((s1 | s2) && len_ch - s2 >= 8 && len_ch + s2 - s1 >= 8) skew = 0x10000 | (s1 << 8) | s2;
       }
     }
@@ -614,8 +600,7 @@ struct FastState<float> {
   // waves per workgroup of the fused iteration kernel: k_fused4 takes 8-wave workgroups (one per CU) once every wave
   // slot is filled; fewer waves than slots: smaller workgroups reach more CUs
   int fused_wgw() const {
-    if (const char* e = getenv("SPECINV_FUSED_WGW")) return atoi(e);           // (experiments)
-    if (SPECINV_R8_W3 && R == 8 && OV == 4 && !use_template) {
+    if (R == 8 && OV == 4 && !use_template) {
       // three waves per SIMD: a 12-wave workgroup is a whole CU, and 8-wave workgroups do not pair up there (2 + 2 waves on a SIMD
       // that holds 3: at 2048 ... 3071 waves every CU's second workgroup waited for the first - round 5's sweep, B 64 x T 300:
       // 316 M against 400 M at B 48).  Below a full chip, 4-wave workgroups: three fit a CU.
@@ -625,9 +610,9 @@ struct FastState<float> {
     // C2 25.8 vs 26.3 ms per step on one box, three runs each - the opposite of k_fused4)
     // ... except when the chunks are skewed (begin_t): one 8-wave workgroup per CU makes the hardware slot of a wave its index in
     // the workgroup / 4, whatever else runs on the chip - the 4-wave form has to infer it from the dispatch order (measured with
-    // the skew: 19.89-20.09 against 20.02-20.16 ms per C2 step, tools/log/r03_wgw8.sh)
+    // the skew: 19.89-20.09 against 20.02-20.16 ms per C2 step, tools/log/EXPERIMENTS.md r03 wgw8)
     if (td && R == 16 && OV == 4) return (skew != 0 && skew < 0x10000) ? 8 : 4;
-    if ((R == 8 || R == 16) && OV == 4 && !use_template) return n_waves >= 2048 ? SPECINV_WGW : 4;
+    if ((R == 8 || R == 16) && OV == 4 && !use_template) return n_waves >= 2048 ? fast::kFused4Waves : 4;
     return 4;
   }
   // {waves per workgroup, chunks per item, waves, kernel: 1 k_fused4, 2 k_fused<R, OV>, 3 k_semi, 4 k_hop, 5 k_fused_td<R, 4> at n_fft 1024 / 2048, 6 k_fused_td<R, OV> otherwise}
@@ -663,30 +648,8 @@ struct FastState<float> {
     const size_t lds_used = G::lds_bytes(wgw);
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
     fast::FastArgs args = a;
-#if SPECINV_K4_STAMPS      // diagnostic build (-DSPECINV_K4_STAMPS=1): the 20th launch's waves to $SPECINV_K4_STAMP_DUMP, tools/td_waves.py format
-    static unsigned long long* d_k4 = nullptr;
-    static int k4_launches = 0;
-    if (!d_k4) SI_HIP(hipMalloc(&d_k4, (size_t)n_waves * 4 * sizeof(unsigned long long)));
-    args.stamps = d_k4;
-#endif
     void* kargs[] = {&args};
     SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds_used, pl.stream));
-#if SPECINV_K4_STAMPS
-    if (++k4_launches == 20) {
-      if (const char* dump = getenv("SPECINV_K4_STAMP_DUMP")) {
-        std::vector<unsigned long long> h((size_t)n_waves * 4);
-        SI_HIP(hipMemcpy(h.data(), d_k4, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        for (int wv = 0; wv < n_waves; ++wv) t0 = std::min(t0, h[4 * (size_t)wv + 1]);
-        if (FILE* f = fopen(dump, "w")) {
-          for (int wv = 0; wv < n_waves; ++wv)
-            fprintf(f, "40 %d %u %u %llu %llu %llu\n", wv, (unsigned)(h[4 * (size_t)wv] >> 32), (unsigned)h[4 * (size_t)wv],
-                    h[4 * (size_t)wv + 1] - t0, h[4 * (size_t)wv + 2] - t0, h[4 * (size_t)wv + 3]);
-          fclose(f);
-        }
-      }
-    }
-#endif
     return SPECINV_OK;
   }
 
@@ -716,58 +679,8 @@ struct FastState<float> {
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
     fast::FastArgs args = a;
-#if SPECINV_TD_STAMPS
-    static unsigned long long* d_stamps = nullptr;
-    if (!d_stamps) SI_HIP(hipMalloc(&d_stamps, (size_t)n_waves * 11 * sizeof(unsigned long long)));
-    args.stamps = d_stamps;
-#endif
     void* kargs[] = {&args};
     SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds_used, pl.stream));
-#if SPECINV_TD_STAMPS
-    if (td_t == 40 || td_t == 5) {
-      std::vector<unsigned long long> h((size_t)n_waves * 11);
-      SI_HIP(hipMemcpy(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      const char* names[6] = {"loads + window + slide", "forward FFT", "split / project / fold", "inverse FFT", "window + out + OLA", "loop"};
-      double tot[6] = {0}, frames = 0;
-      for (int wv = 0; wv < n_waves; ++wv) {
-        for (int i = 0; i < 6; ++i) tot[i] += (double)h[(size_t)wv * 8 + i];
-        frames += (double)h[(size_t)wv * 8 + 6];
-      }
-      fprintf(stderr, "k_fused4_td<%d, early=%d, eval=%d> iteration %d: cycles per frame (s_memtime, mean over %d waves)\n", R, (int)early, (int)ev, td_t, n_waves);
-      double all = 0;
-      for (int i = 0; i < 6; ++i) {
-        fprintf(stderr, "  %-24s %8.0f\n", names[i], tot[i] / frames);
-        all += tot[i] / frames;
-      }
-      fprintf(stderr, "  %-24s %8.0f\n", "frame", all);
-      // how evenly the waves finish: every wave walks the same number of frames, a launch lasts as long as its slowest wave
-      std::vector<double> per_wave((size_t)n_waves);
-      for (int wv = 0; wv < n_waves; ++wv) {
-        double t = 0;
-        for (int i = 0; i < 6; ++i) t += (double)h[(size_t)wv * 8 + i];
-        per_wave[(size_t)wv] = t;
-      }
-      std::sort(per_wave.begin(), per_wave.end());
-      double mean = 0;
-      for (double v : per_wave) mean += v / n_waves;
-      if (const char* dump = getenv("SPECINV_TD_STAMP_DUMP")) {     // wave, xcc, hw_id, begin, end, frames: one line per wave
-        FILE* f = fopen(dump, td_t == 5 ? "w" : "a");
-        if (f) {
-          unsigned long long t0 = ~0ull;
-          for (int wv = 0; wv < n_waves; ++wv) t0 = std::min(t0, h[(size_t)n_waves * 8 + 2 * (size_t)wv + 1]);
-          for (int wv = 0; wv < n_waves; ++wv) {
-            const unsigned long long id = h[(size_t)n_waves * 8 + 2 * (size_t)wv];
-            fprintf(f, "%d %d %u %u %llu %llu %llu\n", td_t, wv, (unsigned)(id >> 32), (unsigned)id,
-                    h[(size_t)n_waves * 8 + 2 * (size_t)wv + 1] - t0, h[(size_t)n_waves * 10 + (size_t)wv] - t0, h[(size_t)wv * 8 + 6]);
-          }
-          fclose(f);
-        }
-      }
-      fprintf(stderr, "  per-wave total: min %.0f  p10 %.0f  median %.0f  mean %.0f  p90 %.0f  p99 %.0f  max %.0f  (max / mean %.3f)\n",
-              per_wave.front(), per_wave[(size_t)(0.1 * n_waves)], per_wave[(size_t)(0.5 * n_waves)], mean,
-              per_wave[(size_t)(0.9 * n_waves)], per_wave[(size_t)(0.99 * n_waves)], per_wave.back(), per_wave.back() / mean);
-    }
-#endif
     return SPECINV_OK;
   }
 

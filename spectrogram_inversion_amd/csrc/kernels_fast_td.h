@@ -21,14 +21,6 @@ namespace SI_FAST_NS {
 //   a.x_in / a.x_out  : z_t / z_{t+1}          a.x2_in / a.x2_out : x_t (EVAL only) / x_{t+1} (nullptr: not wanted)
 //   a.xtail_in / _out : chunk seams, shared by x and z (the - lr * z_t term goes to the block's owner)
 //   a.P_in, a.Pmid_in : c0 pairs (EARLY)        a.tds : (-lr)^t
-#ifndef SPECINV_TD_STAMPS          // diagnostic build: per-phase s_memtime sums of every wave of k_fused4_td (tools/td_stamps.py)
-#define SPECINV_TD_STAMPS 0
-#endif
-#if SPECINV_TD_STAMPS
-#define TD_STAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stamp_sum[i] += now_ - stamp_prev; stamp_prev = now_; } while (0)
-#else
-#define TD_STAMP(i) do { } while (0)
-#endif
 
 template <bool FIRST, typename A, typename B>
 __device__ __forceinline__ const auto& td_pick(const A& a, const B& b) {
@@ -46,18 +38,6 @@ __device__ __forceinline__ void td_load_block(const float* __restrict__ xrow, co
   else load_block<R, OV>(xrow, tailrow, L, T, c, t_begin, t_end, j, lane, pad_mode, q);
 }
 
-#ifndef SPECINV_TD_WKREG
-#define SPECINV_TD_WKREG 1
-#endif
-#ifndef SPECINV_TD_MINWAVES
-#define SPECINV_TD_MINWAVES 2
-#endif
-#ifndef SPECINV_TD_ENVREG          // 1: one block of the (hop-periodic) envelope reciprocal stays in registers (8 at n_fft 2048)
-#define SPECINV_TD_ENVREG 1
-#endif
-#ifndef SPECINV_TD_ABLATE          // timing-only builds (wrong results): 1 target from frame 0 (L2-resident), 2 no output stores,
-#define SPECINV_TD_ABLATE 0        // 4 z samples from the first hop-blocks (L2-resident)
-#endif
 template <int R, int OV, bool EARLY, bool EVAL>
 __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   using G = Geo<R>;
@@ -67,17 +47,16 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   // The synthesis window carries the inverse transform's scale (a second table): one multiplication less per bin pair in the
   // projection; 1 / n_fft is a power of two, so nothing changes in the result (normalized=True never takes this kernel when the
   // reference's operation chain is asked for: FastState::begin_t).
-  constexpr bool WSCALE = SPECINV_IEEE || SPECINV_RSQ;
   v2f* lds_win = reinterpret_cast<v2f*>(smem);
-  v2f* lds_wins = WSCALE ? lds_win + M : lds_win;
-  v2f* lds_tw1 = lds_win + 2 * M;      // (the host reserves both tables for every build: Geo::lds_bytes_td)
+  v2f* lds_wins = lds_win + M;
+  v2f* lds_tw1 = lds_win + 2 * M;      // (Geo::lds_bytes_td)
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   v2f* tr = lds_tw1 + (R - 1) * 64 + wib * G::TR;
 
   for (int i = threadIdx.x; i < M; i += blockDim.x) {
     const v2f wv = v2f{a.window[2 * i], a.window[2 * i + 1]};
     lds_win[i] = wv;
-    if (WSCALE) lds_wins[i] = wv * a.inv_scale;
+    lds_wins[i] = wv * a.inv_scale;
   }
   for (int i = threadIdx.x; i < (R - 1) * 64; i += blockDim.x) {
     const int k1 = i / 64 + 1, l = i & 63;
@@ -95,7 +74,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   // takes the even (longer) chunk of a pair, the younger the odd one.  In 8-wave workgroups (the headline shape) the role is the
   // wave's index in the workgroup / 4.  In 4-wave workgroups (the other overlaps) it is inferred from the dispatch order: the
   // dispatcher hands every CU its first workgroup before any gets a second, so the first half of the waves are the older ones
-  // (1024 of 1024 in every dump of tools/td_waves.py; a launch placed differently is merely less balanced).  (Drawing the chunk
+  // (1024 of 1024 in every wave dump of DESIGN 3.2; a launch placed differently is merely less balanced).  (Drawing the chunk
   // by the slot actually occupied, with two atomic counters, balanced the waves to 4 % - and cost more in 1024 same-address
   // atomics per counter than it won.)
   int b = w / a.nchunks, c = w - b * a.nchunks;
@@ -115,7 +94,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     const int half = a.n_waves >> 1, second = w >= half ? 1 : 0, wl = w - second * half, pairs = a.nchunks >> 1;
     b = wl / pairs;
     c = 2 * (wl - b * pairs) + second;
-    w = b * a.nchunks + c;      // (the index of the chunk walked: partial sums and stamps go by it)
+    w = b * a.nchunks + c;      // (the index of the chunk walked: the partial sums go by it)
   }
   if (a.skew != 0 && w >= a.n_waves) return;
   const int t_begin = chunk_begin(c, a.T, a.nchunks, a.skew);
@@ -137,7 +116,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   double sd = 0.0, so = 0.0;
   // pass-1 twiddles in registers - except in the evaluating variants (one launch in ten), which have no room for them at
   // n_fft 2048 and read the LDS table instead (measured: the same step time, no spills in the late one)
-  constexpr bool TWLDS = (EVAL && R >= 16) || SPECINV_TD_MINWAVES == 3;
+  constexpr bool TWLDS = EVAL && R >= 16;
   TwRegs<TWLDS ? 2 : R> twr_regs;
   if (!TWLDS) {
 #pragma unroll
@@ -156,7 +135,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   // The overlap-add envelope is periodic in the hop wherever all n_fft / hop frames that cover a sample exist (hop-blocks NB .. T-1:
   // the same summands in the same order, plan_impl.h): one block of its reciprocal is kept in registers instead of being loaded for
   // every frame (the evaluating variant has no registers to spare and keeps loading)
-  constexpr bool ENVREG = !EVAL && SPECINV_TD_ENVREG;
+  constexpr bool ENVREG = !EVAL;
   v2f envc[ENVREG ? QU : 1];
   v2f envr[(ENVREG && SPECINV_IEEE) ? QU : 1];     // (reference chain: the envelope block and its correctly rounded reciprocal)
   if (ENVREG) {
@@ -167,21 +146,15 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       if (SPECINV_IEEE) envr[SPECINV_IEEE ? i : 0] = env_rcp(envc[i]);
     }
   }
-#if SPECINV_TD_STAMPS
-  unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
-  const unsigned long long stamp_begin = stamp_prev;
-#endif
   // the real-FFT twiddles of the pairs, W_N^(lane + 64 j): the plain launches have the registers to keep all of them (two waves
   // per SIMD leave 256 each), the others rebuild them from W_N^lane every frame
-  constexpr bool WKREG = !EVAL && SPECINV_TD_MINWAVES == 2 && SPECINV_TD_WKREG;
+  constexpr bool WKREG = !EVAL;
   v2f wkr[WKREG ? H : 1];
   if (WKREG) {
 #pragma unroll
     for (int j = 0; j < H; ++j) wkr[j] = pair_twiddle<R>(k.wn, j);
   }
   for (int t = t_begin; t < t_end; ++t) {
-    TD_STAMP(5);                       // (loop overhead / nothing on the first pass)
     asm volatile("" ::: "memory");     // (window / twiddle reads stay inside the loop: hoisted they pin ~80 VGPRs)
     v2f wn = k.wn;
     asm volatile("" : "+v"(wn));
@@ -192,7 +165,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     float mmid = 0.0f;
     __builtin_amdgcn_s_setprio(1);
     {
-      const v4f* min_ = a.m_pairs + ((SPECINV_TD_ABLATE & 1) ? (long long)(fi & 255) : fi) * (H / 2 * 64);
+      const v4f* min_ = a.m_pairs + fi * (H / 2 * 64);
 #pragma unroll
       for (int j = 0; j < H / 2; ++j) mm[j] = ld_stream(&min_[j * 64u + ulane]);
       if (lane == 0) {
@@ -269,12 +242,10 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       xq[NB - 1][i] = xn[i];
     }
     if (t + 1 < t_end)
-      td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, (SPECINV_TD_ABLATE & 4) ? 8 + (t & 3) : t + OV, lane, a.pad_mode, xn);
+      td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
     __builtin_amdgcn_s_setprio(0);
-    TD_STAMP(0);
 
     fft_forward_t<R>(z, k, twr, tr);
-    TD_STAMP(1);
 
     v2f rc[H];
 #pragma unroll
@@ -286,30 +257,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 
     // ---- per pair: split -> (+ c0 term) -> projection -> fold back
     v2f back[H];
-#if SPECINV_IEEE && !SPECINV_REFBREADTH
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-      const v2f wk = WKREG ? wkr[WKREG ? j : 0] : pair_twiddle<R>(wn, j);
-      v2f sk, sm;
-      td_split_raw<R>(z[j], rc[R - 1 - j - H], wk, sk, sm);
-      if (EARLY) {
-        sk = __builtin_elementwise_fma(v2f{pp[j].x, pp[j].y}, v2f{tds_raw, tds_raw}, sk);
-        sm = __builtin_elementwise_fma(v2f{pp[j].z, pp[j].w}, v2f{tds_raw, tds_raw}, sm);
-      }
-      const v2f rr = ref_rcp_abs2(v2f{ref_norm2(sk, 4.0f * kRefFloor), ref_norm2(sm, 4.0f * kRefFloor)}, 2e-16f);
-      const v2f mp = (j & 1) ? v2f{mm[j / 2].z, mm[j / 2].w} : v2f{mm[j / 2].x, mm[j / 2].y};
-      v2f ak = scale_lo(scale_lo(sk, mp), rr);
-      v2f am = scale_hi(scale_hi(sm, mp), rr);
-      if (j == 0 && lane == 0) {   // bins 0 and M: irfft ignores their imaginary parts
-        ak.y = 0.0f;
-        am.y = 0.0f;
-      }
-      const v2f e2i = add_conj(ak, am);
-      const v2f o2i = cmulc(sub_conj(ak, am), wk);
-      z[j] = add_i(e2i, o2i);
-      back[j] = conj_sub_i(e2i, o2i);
-    }
-#elif SPECINV_IEEE
+#if SPECINV_IEEE
     // The reference's operation order (ref_rcp_abs2, fast_core.h), written breadth-first over the frame's H pairs: every step of
     // the chain of dependent packed operations is issued for all pairs before the next one, so that no instruction waits on the
     // one just before it (the compiler pads such pairs with s_nop: 44 in the frame loop instead of 106).
@@ -327,20 +275,6 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       }
 #pragma unroll
       for (int j = 0; j < H; ++j) yy[j] = v2f{__builtin_amdgcn_rsqf(tt[j].x), __builtin_amdgcn_rsqf(tt[j].y)};
-#if SPECINV_REFCHAIN == 1
-#pragma unroll
-      for (int j = 0; j < H; ++j) hh[j] = tt[j] * yy[j];
-#pragma unroll
-      for (int j = 0; j < H; ++j) tt[j] = __builtin_elementwise_fma(-hh[j], hh[j], tt[j]);        // residual t - h^2
-#pragma unroll
-      for (int j = 0; j < H; ++j) hh[j] = __builtin_elementwise_fma(tt[j], yy[j] * 0.5f, hh[j]);  // RN(sqrt t)
-#pragma unroll
-      for (int j = 0; j < H; ++j) hh[j] = hh[j] + 2e-16f;                                           // (+ 1e-16 at the true scale)
-#pragma unroll
-      for (int j = 0; j < H; ++j) tt[j] = __builtin_elementwise_fma(-hh[j], yy[j], v2f{1.0f, 1.0f});
-#pragma unroll
-      for (int j = 0; j < H; ++j) yy[j] = __builtin_elementwise_fma(tt[j], yy[j], yy[j]);          // RN(1 / (|s| + 1e-16))
-#else
       // one Newton step on y ~ t^-1/2: the correctly rounded 1 / |s| in all but ~1e-6 of the cases (ONE rounding of the exact
       // value where the reference rounds |s| and then its reciprocal); the guard 1e-16 only matters below |s| = 3e-9
 #pragma unroll
@@ -349,7 +283,6 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       for (int j = 0; j < H; ++j) tt[j] = __builtin_elementwise_fma(-hh[j], yy[j], v2f{1.0f, 1.0f});
 #pragma unroll
       for (int j = 0; j < H; ++j) yy[j] = __builtin_elementwise_fma(yy[j] * 0.5f, tt[j], yy[j]);
-#endif
 #pragma unroll
       for (int j = 0; j < H; ++j) {
         const v2f mp = (j & 1) ? v2f{mm[j / 2].z, mm[j / 2].w} : v2f{mm[j / 2].x, mm[j / 2].y};
@@ -376,37 +309,23 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     for (int j = 0; j < H; ++j) {
       const v2f wk = WKREG ? wkr[WKREG ? j : 0] : pair_twiddle<R>(wn, j);
       v2f sk, sm;
-      if (!SPECINV_RSQ) {
-        td_split<R>(z[j], rc[R - 1 - j - H], wk, half_scale, sk, sm);
-        if (EARLY) {
-          sk = v2f{fmaf(a.tds, pp[j].x, sk.x), fmaf(a.tds, pp[j].y, sk.y)};
-          sm = v2f{fmaf(a.tds, pp[j].z, sm.x), fmaf(a.tds, pp[j].w, sm.y)};
-        }
-      } else {
-        // nothing but the projection reads the bins, and it divides by their magnitude: the 1/2 fwd_scale of the split is left
-        // out (late launches) or moved onto the c0 term's factor (early launches: S / s = raw + (tds / s) c0, one packed
-        // multiply-add per bin).  With the reference's operation chain (SPECINV_IEEE) this is exact, not approximate: the
-        // kernel is only taken for fwd_scale = 1, the factor 2 scales every intermediate result without a rounding, and the
-        // guard / floor constants are doubled / quadrupled with it.
-        td_split_raw<R>(z[j], rc[R - 1 - j - H], wk, sk, sm);
-        if (EARLY) {
-          sk = __builtin_elementwise_fma(v2f{pp[j].x, pp[j].y}, v2f{tds_raw, tds_raw}, sk);
-          sm = __builtin_elementwise_fma(v2f{pp[j].z, pp[j].w}, v2f{tds_raw, tds_raw}, sm);
-        }
+      // nothing but the projection reads the bins, and it divides by their magnitude: the 1/2 fwd_scale of the split is left
+      // out (late launches) or moved onto the c0 term's factor (early launches: S / s = raw + (tds / s) c0, one packed
+      // multiply-add per bin).  With the reference's operation chain (SPECINV_IEEE) this is exact, not approximate: the
+      // kernel is only taken for fwd_scale = 1, the factor 2 scales every intermediate result without a rounding, and the
+      // guard / floor constants are doubled / quadrupled with it.
+      td_split_raw<R>(z[j], rc[R - 1 - j - H], wk, sk, sm);
+      if (EARLY) {
+        sk = __builtin_elementwise_fma(v2f{pp[j].x, pp[j].y}, v2f{tds_raw, tds_raw}, sk);
+        sm = __builtin_elementwise_fma(v2f{pp[j].z, pp[j].w}, v2f{tds_raw, tds_raw}, sm);
       }
       const float mk = (j & 1) ? mm[j / 2].z : mm[j / 2].x;
       const float mq = (j & 1) ? mm[j / 2].w : mm[j / 2].y;
-#if SPECINV_RSQ
       // the projection's factors (proj_rsq, fast_core.h) of the pair's two bins, formed and applied as packed operations
       const v2f inv = v2f{proj_rsq(sk), proj_rsq(sm)};
       const v2f mi = v2f{mk, mq} * inv;                       // (the inverse scale rides on the synthesis window)
       v2f ak = scale_lo(sk, mi);
       v2f am = scale_hi(sm, mi);
-#else
-      const float ik = fast_rcp(fast_abs(sk) + 1e-16f) * a.inv_scale, iq = fast_rcp(fast_abs(sm) + 1e-16f) * a.inv_scale;
-      v2f ak = v2f{(sk.x * mk) * ik, (sk.y * mk) * ik};
-      v2f am = v2f{(sm.x * mq) * iq, (sm.y * mq) * iq};
-#endif
       if (j == 0 && lane == 0) {   // bins 0 and M: irfft ignores their imaginary parts
         ak.y = 0.0f;
         am.y = 0.0f;
@@ -423,11 +342,8 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       if (EARLY) smid = v2f{fmaf(a.tds, pmid.x, smid.x), fmaf(a.tds, pmid.y, smid.y)};
 #if SPECINV_IEEE
       const v2f am = (smid * mmid) * ref_rcp_abs(ref_norm2(smid));
-#elif SPECINV_RSQ
-      const v2f am = smid * (mmid * proj_rsq(smid));
 #else
-      const float inv = fast_rcp(fast_abs(smid) + 1e-16f) * a.inv_scale;
-      const v2f am = v2f{(smid.x * mmid) * inv, (smid.y * mmid) * inv};
+      const v2f am = smid * (mmid * proj_rsq(smid));
 #endif
       zmid = am * v2f{2.0f, -2.0f};
     }
@@ -437,10 +353,8 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       const v2f l0 = (m == H) ? zmid : back[(R - m) % H];
       z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
     }
-    TD_STAMP(2);
 
     fft_inverse_t<R>(z, k, twr, tr);
-    TD_STAMP(3);
 
     // ---- synthesis window, register overlap-add, one finished hop-block of x_{t+1} and of z_{t+1} out
 #pragma unroll
@@ -479,10 +393,8 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       for (int i = 0; i < QU; ++i) {
         const v2f xv = env_apply_r(acc[i] + z[i], ev[i], er[i]);
         const v2f zv = v2f{fmaf(nlr, zold[i].x, xv.x), fmaf(nlr, zold[i].y, xv.y)};
-        if (!(SPECINV_TD_ABLATE & 2) || zv.x == 1.2345e30f) {
-          if (write_x) xo[64u * i + ulane] = xv;
-          zo[64u * i + ulane] = zv;
-        }
+        if (write_x) xo[64u * i + ulane] = xv;
+        zo[64u * i + ulane] = zv;
       }
     }
 #pragma unroll
@@ -491,22 +403,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       for (int q = 0; q + 1 < NB; ++q) acc[q * QU + i] = acc[(q + 1) * QU + i] + z[(q + 1) * QU + i];
       acc[(NB - 1) * QU + i] = z[NB * QU + i];
     }
-    TD_STAMP(4);
   }
-#if SPECINV_TD_STAMPS
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a.stamps[(long long)w * 8 + i] = stamp_sum[i];
-    a.stamps[(long long)w * 8 + 6] = (unsigned long long)(t_end - t_begin);
-    // where and when the wave ran: HW_ID (wave / SIMD / CU / SH / SE) with the XCC id above it, begin and end in the low / high
-    // halves of one word (differences to the launch's earliest begin fit 32 bits)
-    const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID, 32 bits
-    const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-    a.stamps[(long long)a.n_waves * 8 + 2 * (long long)w] = ((unsigned long long)xcc << 32) | hw;
-    a.stamps[(long long)a.n_waves * 8 + 2 * (long long)w + 1] = stamp_begin;
-    a.stamps[(long long)a.n_waves * 10 + (long long)w] = __builtin_amdgcn_s_memtime();
-  }
-#endif
   if (t_end == a.T) {
     // the chunk that holds the last frame also finishes hop-blocks T .. T + PB - 2 (the frames that reach them are done);
     // xq[q] is z_t's block T + q by now
@@ -544,13 +441,12 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 
 // the headline shapes (hop = n_fft/4 at n_fft 1024 / 2048) launch 8-wave workgroups, one per CU, like k_fused4
 template <int R, bool EARLY, bool EVAL>
-__global__ __launch_bounds__((SPECINV_TD_MINWAVES == 3 || (SPECINV_R8_W3 && R == 8)) ? 768 : 64 * SPECINV_WGW,
-                            (SPECINV_R8_W3 && R == 8) ? 3 : SPECINV_TD_MINWAVES) void k_fused4_td(FastArgs a) {
+__global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves : kMinWaves) void k_fused4_td(FastArgs a) {
   fused_td_body<R, 4, EARLY, EVAL>(a);
 }
 // every other fused shape: 4-wave workgroups like k_fused<R, OV>
 template <int R, int OV, bool EARLY, bool EVAL>
-__global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : SPECINV_MINWAVES) void k_fused_td(FastArgs a) {
+__global__ __launch_bounds__(256, R >= 32 ? 1 : R == 8 ? kR8Waves : kMinWaves) void k_fused_td(FastArgs a) {
   fused_td_body<R, OV, EARLY, EVAL>(a);
 }
 
@@ -561,12 +457,9 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
 // on the same stream - it is a forward transform and a sum with the sample window carried from frame to frame like the
 // iteration's: 0.12 ms.  A wave walks one of kEvalSub pieces of a chunk of the iteration's chunking (whose seams the block
 // loader resolves).  Same operations in the same order as the EVAL block of fused_td_body: the same sums, bit for bit.
-#ifndef SPECINV_EVAL_TWREGS
-#define SPECINV_EVAL_TWREGS 1
-#endif
 constexpr int kEvalSub = kEvalPieces;
 template <int R, int OV>
-__global__ __launch_bounds__(256, SPECINV_EVAL_WAVES) void k_eval_td(FastArgs a) {
+__global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a) {
   using G = Geo<R>;
   using O = Ovl<R, OV>;
   constexpr int H = G::H, M = G::M, QU = O::QU, HOP = O::HOP, NB = O::NB;
@@ -593,13 +486,9 @@ __global__ __launch_bounds__(256, SPECINV_EVAL_WAVES) void k_eval_td(FastArgs a)
   const float* xrow = a.x2_in + (long long)b * a.L;
   const float* tailrow = a.xtail_in + (long long)b * a.nchunks * NB * HOP;
   const float half_scale = 0.5f * a.fwd_scale;
-#if SPECINV_EVAL_TWREGS
   TwRegs<R> twr;
 #pragma unroll
   for (int k1 = 1; k1 < R; ++k1) twr.w[k1 - 1] = lds_tw1[(k1 - 1) * 64 + lane];
-#else
-  const TwLds twr{lds_tw1, lane};
-#endif
   double sd = 0.0, so = 0.0;
   v2f xq[NB][QU], xn[QU];
 #pragma unroll

@@ -2,15 +2,12 @@
 #pragma once
 #include "fast_core.h"
 
-#ifndef SPECINV_K4_STAMPS
-#define SPECINV_K4_STAMPS 0
-#endif
 
 namespace specinv {
 namespace SI_FAST_NS {
 
 template <int R, int MODE, bool EVAL>
-__global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW, (SPECINV_R8_W3 && R == 8) ? 3 : SPECINV_MINWAVES) void k_fused4(FastArgs a) {
+__global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves : kMinWaves) void k_fused4(FastArgs a) {
   using G = Geo<R>;
   constexpr int H = G::H, QU = G::QU, M = G::M, HOP = G::HOP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -30,9 +27,6 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
 
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);   // (scalar: the frame loop and its padding tests branch on the scalar unit; left to the compiler the work-group size may arrive in a vector register and make all of it per-lane)
   if (w >= a.n_waves) return;
-#if SPECINV_K4_STAMPS
-  const unsigned long long k4_begin = __builtin_amdgcn_s_memtime();
-#endif
   const LaneConst<R> k = lane_consts<R>();
   const int lane = k.lane;
   const unsigned ulane = (unsigned)lane;
@@ -59,40 +53,25 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
   for (int i = 0; i < 3 * QU; ++i) acc[i] = v2f{0.0f, 0.0f};
   double sd = 0.0, so = 0.0;
   // one block of the envelope reciprocal, periodic in the hop from hop-block 3 on (kernels_fast_td.h), kept in registers
-  v2f envc[SPECINV_K4_ENVREG ? QU : 1];
-  v2f envr[(SPECINV_K4_ENVREG && SPECINV_IEEE) ? QU : 1];   // (reference chain: the envelope and its correctly rounded reciprocal)
-  if (SPECINV_K4_ENVREG) {
-    const v2f* e0 = reinterpret_cast<const v2f*>(a.inv_env + (long long)HOP);
+  v2f envc[QU];
+  v2f envr[SPECINV_IEEE ? QU : 1];   // (reference chain: the envelope and its correctly rounded reciprocal)
+  const v2f* e0 = reinterpret_cast<const v2f*>(a.inv_env + (long long)HOP);
 #pragma unroll
-    for (int i = 0; i < QU; ++i) {
-      envc[i] = e0[64u * i + ulane];
-      if (SPECINV_IEEE) envr[SPECINV_IEEE ? i : 0] = env_rcp(envc[i]);
-    }
+  for (int i = 0; i < QU; ++i) {
+    envc[i] = e0[64u * i + ulane];
+    if (SPECINV_IEEE) envr[SPECINV_IEEE ? i : 0] = env_rcp(envc[i]);
   }
-#if SPECINV_TW_REGS
   TwRegs<R> twr;
 #pragma unroll
   for (int k1 = 1; k1 < R; ++k1) twr.w[k1 - 1] = lds_tw1[(k1 - 1) * 64 + lane];
-#endif
 
   // raw samples of the current frame: three hop-blocks carried from frame to frame plus the
   // new one, which is fetched one frame ahead so that its latency hides behind a whole frame
-#if SPECINV_XPREF == 2
-  v2f znext[R];
-#pragma unroll
-  for (int qq = 0; qq < 4; ++qq) {
-    v2f q[QU];
-    load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t_start + qq, lane, a.pad_mode, q);
-#pragma unroll
-    for (int i = 0; i < QU; ++i) znext[qq * QU + i] = q[i];
-  }
-#elif SPECINV_XPREF == 1
   v2f xq[3][QU], xn[QU];
   load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t_start, lane, a.pad_mode, xq[0]);
   load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t_start + 1, lane, a.pad_mode, xq[1]);
   load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t_start + 2, lane, a.pad_mode, xq[2]);
   load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t_start + 3, lane, a.pad_mode, xn);
-#endif
 
   // state of frame `FI`: uniform bases (SGPR) + unsigned 32-bit lane offsets -> "saddr + voffset" addressing
 #define SPECINV_STATE_LOADS4(FI)                                                            \
@@ -107,12 +86,6 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
       mmid = a.m_mid[fl_];                                                                 \
     }                                                                                      \
   } while (0)
-#if SPECINV_PLATE == 2
-  v4f pp[H], mm[H / 2];
-  v2f pmid = v2f{0.0f, 0.0f}, umid = v2f{0.0f, 0.0f};
-  float mmid = 0.0f;
-  SPECINV_STATE_LOADS4((long long)b * a.T + t_start);
-#endif
 
   for (int t = t_start; t < t_end; ++t) {
     // Keep the loop-invariant table reads (window, twiddles) and products inside the loop: hoisted out
@@ -124,24 +97,16 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
     const long long fi = (long long)b * a.T + t;
     v4f* pout = a.P_out + fi * (H * 64);
     const bool keep_xu = MODE == MODE_ADMM && a.U_out != nullptr;   // (uniform: a kernel argument)
-#if SPECINV_PLATE != 2
     v4f pp[H], mm[H / 2];
     v2f pmid = v2f{0.0f, 0.0f}, umid = v2f{0.0f, 0.0f};
     float mmid = 0.0f;
-#endif
-#if SPECINV_PLATE == 0
-#if SPECINV_PRIO
-    __builtin_amdgcn_s_setprio(SPECINV_PRIO & 3);
-#endif
+    // priority 1 while the state loads and the sample prefetch are issued, so that they do not queue behind the other wave's FFT
+    // (C2: 0.3023 -> 0.2997 ms per launch)
+    __builtin_amdgcn_s_setprio(1);
     SPECINV_STATE_LOADS4(fi);   // early: the loads fly during the forward FFT
-#endif
 
     // ---- analysis: windowed frame -> registers
     v2f z[R];
-#if SPECINV_XPREF == 2
-#pragma unroll
-    for (int u = 0; u < R; ++u) z[u] = znext[u] * lds_win[64 * u + lane];
-#elif SPECINV_XPREF == 1
     // slide the sample window and prefetch the next hop-block
 #pragma unroll
     for (int i = 0; i < QU; ++i) {
@@ -154,32 +119,9 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
       xq[2][i] = xn[i];
     }
     if (t + 1 < t_end) load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + 4, lane, a.pad_mode, xn);
-#if SPECINV_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
-#else
-    {
-      v2f q[QU];
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + qq, lane, a.pad_mode, q);
-#pragma unroll
-        for (int i = 0; i < QU; ++i) z[qq * QU + i] = q[i];
-      }
-#pragma unroll
-      for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
-    }
-#endif
 
-#if SPECINV_ABLATE & 4
-#elif SPECINV_TW_REGS
     fft_forward_t<R>(z, k, twr, tr);
-#else
-    fft_forward<R>(z, k, lds_tw1, tr);
-#endif
-#if SPECINV_PLATE == 1
-    SPECINV_STATE_LOADS4(fi);
-#endif
 
     // ---- conjugate partners: upper half of lane (64 - r)
     v2f rc[H];   // rc[i] pairs with own register H-1-i ... see below: rc[m-H] = Z[M - (lane + 64*(R-1-m))]
@@ -249,38 +191,12 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
       const v2f l0 = (m == H) ? zmid : back[(R - m) % H];
       z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
     }
-#if SPECINV_PLATE == 2
-    // the state registers are free again: fetch the next frame's state now, it flies through the inverse FFT,
-    // the overlap-add and the next forward FFT
-    if (t + 1 < t_end) SPECINV_STATE_LOADS4(fi + 1);
-#endif
 
-#if SPECINV_XPREF == 2
-    if (t + 1 < t_end) {
-#pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        v2f q[QU];
-        load_block4<R>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + 1 + qq, lane, a.pad_mode, q);
-#pragma unroll
-        for (int i = 0; i < QU; ++i) znext[qq * QU + i] = q[i];
-      }
-    }
-#endif
-
-#if SPECINV_ABLATE & 4
-#elif SPECINV_TW_REGS
     fft_inverse_t<R>(z, k, twr, tr);
-#else
-    asm volatile("" ::: "memory");   // re-read the twiddles instead of keeping them live since the forward FFT
-    fft_inverse<R>(z, k, lds_tw1, tr);
-#endif
 
     // ---- synthesis window, register overlap-add, one finished hop-block out
 #pragma unroll
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
-#if SPECINV_PRIO & 4
-    __builtin_amdgcn_s_setprio(3);
-#endif
     if (live && t >= 2) {
       const long long o0 = (long long)(t - 2) * HOP;
       const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);   // uniform
@@ -288,17 +204,11 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
       // (the envelope block: register copy, or - first frames of an item - loaded and waited for in an arm of its own; see
       // fused_td_body, kernels_fast_td.h)
       v2f ev[QU], er[QU];
-      if (!SPECINV_K4_ENVREG) {
+      if (t >= 3) {
 #pragma unroll
         for (int i = 0; i < QU; ++i) {
-          ev[i] = envp[64u * i + ulane];
-          er[i] = env_rcp(ev[i]);
-        }
-      } else if (t >= 3) {
-#pragma unroll
-        for (int i = 0; i < QU; ++i) {
-          ev[i] = envc[SPECINV_K4_ENVREG ? i : 0];
-          er[i] = envr[(SPECINV_K4_ENVREG && SPECINV_IEEE) ? i : 0];
+          ev[i] = envc[i];
+          er[i] = envr[SPECINV_IEEE ? i : 0];
         }
       } else {
 #pragma unroll
@@ -311,9 +221,6 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
 #pragma unroll
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply_r(acc[i] + z[i], ev[i], er[i]);
     }
-#if SPECINV_PRIO & 4
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
     for (int i = 0; i < QU; ++i) {
       acc[i] = acc[QU + i] + z[QU + i];
@@ -345,20 +252,10 @@ __global__ __launch_bounds__((SPECINV_R8_W3 && R == 8) ? 768 : 64 * SPECINV_WGW,
       a.partials[2 * (long long)w + 1] = o;
     }
   }
-#if SPECINV_K4_STAMPS   // diagnostic build: where and when the wave ran (tools/td_waves.py reads the dump)
-  if (lane == 0 && a.stamps != nullptr) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-    const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
-    a.stamps[4 * (long long)w] = ((unsigned long long)xcc << 32) | hw;
-    a.stamps[4 * (long long)w + 1] = k4_begin;
-    a.stamps[4 * (long long)w + 2] = __builtin_amdgcn_s_memtime();
-    a.stamps[4 * (long long)w + 3] = (unsigned long long)(t_end - t_begin);
-  }
-#endif
 }
 
 template <int R, int OV, int MODE, bool EVAL>
-__global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : SPECINV_MINWAVES) void k_fused(FastArgs a) {
+__global__ __launch_bounds__(256, R >= 32 ? 1 : R == 8 ? kR8Waves : kMinWaves) void k_fused(FastArgs a) {
   using G = Geo<R>;
   using O = Ovl<R, OV>;
   constexpr int H = G::H, M = G::M, QU = O::QU, HOP = O::HOP, NB = O::NB, PB = O::PB;
@@ -395,11 +292,9 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
 #pragma unroll
   for (int i = 0; i < NB * QU; ++i) acc[i] = v2f{0.0f, 0.0f};
   double sd = 0.0, so = 0.0;
-#if SPECINV_TW_REGS
   TwRegs<R> twr;
 #pragma unroll
   for (int k1 = 1; k1 < R; ++k1) twr.w[k1 - 1] = lds_tw1[(k1 - 1) * 64 + lane];
-#endif
 
   // raw samples of the current frame: NB hop-blocks carried from frame to frame plus the
   // new one, which is fetched one frame ahead so that its latency hides behind a whole frame
@@ -436,9 +331,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
     v4f pp[H], mm[H / 2];
     v2f pmid = v2f{0.0f, 0.0f}, umid = v2f{0.0f, 0.0f};
     float mmid = 0.0f;
-#if SPECINV_PRIO
-    if (R < 32) __builtin_amdgcn_s_setprio(SPECINV_PRIO & 3);   // (one wave per SIMD at R = 32: nothing to outrank)
-#endif
+    if (R < 32) __builtin_amdgcn_s_setprio(1);   // (one wave per SIMD at R = 32: nothing to outrank)
     SPECINV_STATE_LOADS(fi);   // early: the loads fly during the forward FFT
 
     // ---- analysis: windowed frame -> registers; slide the sample window and prefetch the next hop-block
@@ -453,16 +346,9 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
       xq[NB - 1][i] = xn[i];
     }
     if (t + 1 < t_end) load_block<R, OV>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
-#if SPECINV_PRIO
     if (R < 32) __builtin_amdgcn_s_setprio(0);
-#endif
 
-#if SPECINV_ABLATE & 4
-#elif SPECINV_TW_REGS
     fft_forward_t<R>(z, k, twr, tr);
-#else
-    fft_forward<R>(z, k, lds_tw1, tr);
-#endif
 
     // ---- conjugate partners: upper half of lane (64 - r)
     v2f rc[H];   // rc[i] pairs with own register H-1-i ... see below: rc[m-H] = Z[M - (lane + 64*(R-1-m))]
@@ -533,13 +419,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
       z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
     }
 
-#if SPECINV_ABLATE & 4
-#elif SPECINV_TW_REGS
     fft_inverse_t<R>(z, k, twr, tr);
-#else
-    asm volatile("" ::: "memory");   // re-read the twiddles instead of keeping them live since the forward FFT
-    fft_inverse<R>(z, k, lds_tw1, tr);
-#endif
 
     // ---- synthesis window, register overlap-add, one finished hop-block out
 #pragma unroll
@@ -590,7 +470,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : (SPECINV_R8_W3 && R == 8) ? 3 : 
 // ISTFT of a spectrum held in pair layout: x = overlap-add(w * irfft(S)) / envelope  (methods.py:233: the
 // initial signal of griffin_lim / ADMM).  Same wave-per-chunk walk as k_fused, without the analysis half.
 template <int R, int OV>
-__global__ __launch_bounds__(256, R >= 32 ? 1 : SPECINV_MINWAVES) void k_fused_istft(FastArgs a) {
+__global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(FastArgs a) {
   using G = Geo<R>;
   using O = Ovl<R, OV>;
   constexpr int H = G::H, M = G::M, QU = O::QU, HOP = O::HOP, NB = O::NB, PB = O::PB;

@@ -1042,13 +1042,9 @@ inline int obj_mel_tiles(int n_mels, int R) {
 //   * without statistics: loss = scale * sum(partials) by one extra block (block kObjRows), as k_finish_scaled would.
 // A margin sample that also lies in a seam region is finished by its margin thread (own + tail first, then the fold: the order
 // of the separate launches); the seam threads leave those samples alone, so no two threads touch the same sample.
-#ifndef SPECINV_EPI_ABL              // (timing experiments, wrong results: 1 no margins, 2 no statistics arithmetic, 4 no g_prev loads, 8 no seams)
-#define SPECINV_EPI_ABL 0
-#endif
-#ifndef SPECINV_EPI_GROUP            // threads that walk one tile together in the epilogue's statistics pass
-#define SPECINV_EPI_GROUP 128      // (C5: 512 / 256 / 128 -> 122.7 / 121.2 / 120.8 ms per step)
-#endif
 constexpr int kObjEpiThreads = 1024;   // a streaming pass wants waves in flight: 16 per CU at one block per CU
+constexpr int kObjEpiGroup = 128;      // threads that walk one tile together in the statistics pass (C5: 512 / 256 / 128 threads
+                                       // -> 122.7 / 121.2 / 120.8 ms per step)
 // the tail's hand-over of the rows by write-through stores + vmcnt(0) instead of a release (see the tail below): only where the
 // ISA documents it
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
@@ -1132,7 +1128,7 @@ static __global__ __launch_bounds__(kObjEpiThreads) void k_objective_epilogue(fl
       // Two groups of 512 threads walk tiles of their own, three pieces per thread and trip with their loads all requested first:
       // 9 - 12 loads of 16 bytes in flight per thread (four pieces: 46 registers spilled at 16 waves per CU).
       const int64_t n_pairs = rows * nchunks;
-      constexpr int GT = SPECINV_EPI_GROUP, NG = kObjEpiThreads / GT;
+      constexpr int GT = kObjEpiGroup, NG = kObjEpiThreads / GT;
       const int grp = threadIdx.x / GT, tig = threadIdx.x - grp * GT;
       // (b, c) of a group's tiles advance by additions: an integer division per tile - and the plain form had three, one of them
       // 64-bit - is a few hundred vector instructions that every wave of the group repeats (round 5: 15 of the pass's 29 us went
@@ -1167,30 +1163,27 @@ static __global__ __launch_bounds__(kObjEpiThreads) void k_objective_epilogue(fl
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             of[u] = o0 + u * 4 * GT < span ? o0 + u * 4 * GT : o0;
-            gv[u] = (SPECINV_EPI_ABL & 16) ? fast::v4f{1.0f, 2.0f, 3.0f, (float)of[u]} : *reinterpret_cast<const fast::v4f*>(gb + of[u]);
-            pv[u] = (pb && !(SPECINV_EPI_ABL & 4)) ? *reinterpret_cast<const fast::v4f*>(pb + of[u]) : gv[u];
+            gv[u] = *reinterpret_cast<const fast::v4f*>(gb + of[u]);
+            pv[u] = pb ? *reinterpret_cast<const fast::v4f*>(pb + of[u]) : gv[u];
             dv[u] = db ? *reinterpret_cast<const fast::v4f*>(db + of[u]) : gv[u];
             if (d_impl) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) dv[u][e] = d_of(pv[u][e]);
             }
-            tv[u] = (of[u] < seam_end && !(SPECINV_EPI_ABL & 8)) ? *reinterpret_cast<const fast::v4f*>(tl + of[u]) : fast::v4f{0.0f, 0.0f, 0.0f, 0.0f};
+            tv[u] = of[u] < seam_end ? *reinterpret_cast<const fast::v4f*>(tl + of[u]) : fast::v4f{0.0f, 0.0f, 0.0f, 0.0f};
           }
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             if (u > 0 && o0 + u * 4 * GT >= span) continue;
             const int o = of[u];
-            const bool sm = o < seam_end && !(SPECINV_EPI_ABL & 8);
+            const bool sm = o < seam_end;
             if (o > f_lo && o + 3 < f_hi) {
               if (sm) {
                 gv[u] = gv[u] + tv[u];
                 *reinterpret_cast<fast::v4f*>(gb + o) = gv[u];
               }
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                if (SPECINV_EPI_ABL & 2) sta.mg = fmaxf(sta.mg, gv[u][e] + pv[u][e] + dv[u][e]);
-                else sta.add(gv[u][e], pb ? pv[u][e] : gv[u][e], (db || d_impl) ? dv[u][e] : gv[u][e], st_t);
-              }
+              for (int e = 0; e < 4; ++e) sta.add(gv[u][e], pb ? pv[u][e] : gv[u][e], (db || d_impl) ? dv[u][e] : gv[u][e], st_t);
             } else {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
@@ -1252,7 +1245,7 @@ static __global__ __launch_bounds__(kObjEpiThreads) void k_objective_epilogue(fl
     }
   }
   // ---- margins
-  for (int64_t i = first; i < ((SPECINV_EPI_ABL & 1) ? 0 : n_margin); i += stride) {
+  for (int64_t i = first; i < n_margin; i += stride) {
     const int64_t per_row = 2 * ((int64_t)pad + 1);
     const int64_t bi = n_margin < ((int64_t)1 << 31) ? (int64_t)((unsigned)i / (unsigned)per_row) : i / per_row, j = i - bi * per_row;
     int64_t n;
@@ -1302,7 +1295,7 @@ static __global__ __launch_bounds__(kObjEpiThreads) void k_objective_epilogue(fl
   double v[9] = {sta.s[0], sta.s[1], sta.s[2], sta.s[3], sta.s[4], sta.s[5], 0.0, (double)sta.mg, (double)sta.md};
   const int lo = (int)((int64_t)n_part * blockIdx.x / fast::kObjRows), hi = (int)((int64_t)n_part * (blockIdx.x + 1) / fast::kObjRows);
   for (int tl = lo + threadIdx.x; tl < hi; tl += blockDim.x) v[6] += part[tl];
-  if (!(SPECINV_EPI_ABL & 32)) block_reduce9(v, red9);
+  block_reduce9(v, red9);
   const bool tail = dec.ticket != nullptr;
   __shared__ int last;
   if (threadIdx.x == 0) {                       // component-major: readers take one component of every row with one coalesced load
@@ -1437,13 +1430,11 @@ int tf_loss_grad_fused(P& pl, const float* x, int64_t len, const float* target, 
       const int floor_ch = ov == 8 ? 16 : 8;
       int nch = (int)std::max<int64_t>(1, std::min<int64_t>(T / floor_ch, 2048 / std::max(1, B)));
       if (nch > 1 && (nch & 1)) --nch;
-      if (const char* e = getenv("SPECINV_OBJ_WALK_CHUNKS")) nch = std::max(1, std::min(T / floor_ch, atoi(e)));
       const int len_ch = T / nch;
       int skew = 0;
       // (C5, chunks of 8 frames, one box: skew 0 / 1 / 2 / 3 -> 126.1 / 122.0 / 124.9 / 128.0 ms per step: an eighth of the chunk -
       // the contractions' LDS waits leave the younger wave more of the SIMD than the Griffin-Lim kernel's pure transforms do)
       if ((nch & 1) == 0 && (int64_t)B * nch > 1024 && len_ch >= 8) skew = std::max(1, len_ch / 8);
-      if (const char* e = getenv("SPECINV_OBJ_WALK_SKEW")) skew = (nch & 1) == 0 ? std::max(0, atoi(e)) : 0;
       if (len_ch - skew < std::max(ov, 6)) skew = 0;            // (the shorter chunk of a pair still holds its seam and a frame more)
       const int keep = N - hop;
       const int64_t n_waves = (int64_t)B * nch;
@@ -1579,34 +1570,8 @@ int tf_loss_grad_fused(P& pl, const float* x, int64_t len, const float* target, 
 #undef SPECINV_OBJ_CASE
   if (fn == nullptr || lds > 160 * 1024) return SPECINV_OK;
   SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#if SPECINV_OBJ_STAMPS
-  static unsigned long long* d_stamps = nullptr;
-  if (!d_stamps) SI_HIP(hipMalloc(&d_stamps, (size_t)n_tiles * 16 * sizeof(unsigned long long)));
-  a.stamps = d_stamps;
-#endif
   void* kargs[] = {&a};
   SI_HIP(hipLaunchKernel(fn, dim3((unsigned)n_tiles), dim3(64 * fast::kObjWaves), kargs, lds, pl.stream));
-#if SPECINV_OBJ_STAMPS
-  {
-    std::vector<unsigned long long> h((size_t)n_tiles * 16);
-    SI_HIP(hipMemcpy(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    static int calls = 0;
-    if (++calls == 5) {
-      // (band form: "forward GEMM" = staging the bands, its "wait" = the band forward with step 3, "reduce" = the barrier behind it)
-      const char* names[12] = {"tables + twiddle regs", "analysis (2 frames)", "  wait", "forward GEMM", "  wait", "reduce+log1p+dM",
-                               "backward GEMM", "  wait", "synthesis (2 frames)", "  wait", "frames to LDS", "overlap-add"};
-      double tot[13] = {0};
-      for (int64_t t = 0; t < n_tiles; ++t)
-        for (int i = 1; i <= 12; ++i) tot[i] += (double)(h[t * 16 + i] - h[t * 16 + i - 1]);
-      fprintf(stderr, "k_objective_logmel phase cycles (s_memtime; mean over %lld tiles, wave %d of the workgroup; 'wait' = at the barrier):\n", (long long)n_tiles, SPECINV_OBJ_STAMP_WAVE);
-      for (int i = 1; i <= 11; ++i) fprintf(stderr, "  %-22s %9.0f\n", names[i - 1], tot[i] / n_tiles);
-      fprintf(stderr, "  %-22s %9.0f\n", "write-out", tot[12] / n_tiles);
-      double all = 0;
-      for (int64_t t = 0; t < n_tiles; ++t) all += (double)(h[t * 16 + 12] - h[t * 16]);
-      fprintf(stderr, "  %-22s %9.0f\n", "whole tile", all / n_tiles);
-    }
-  }
-#endif
   *used = true;
   pl.objective_kind = sparse ? 2 : 1;
   {

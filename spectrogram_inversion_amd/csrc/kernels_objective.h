@@ -38,13 +38,6 @@ __device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-#if SPECINV_OBJ_STAMPS
-#define OBJ_STAMP(i) do { if (threadIdx.x == 64 * SPECINV_OBJ_STAMP_WAVE) a.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OBJ_STAMP(i) do { } while (0)
-#endif
-
-
 // Step 3 for one output: d = log1p(v) - target, the squared error, dM = dscale d / (1 + v)  (v = (Mel |S|)[m, n] >= 0).
 //   log1p(v) = log(u) + (v - (u - 1)) / u with u = fl(1 + v): the second term restores what the rounding of 1 + v lost (a third of
 //   log1pf's instructions, the same result to an ulp); 1 / u: v_rcp_f32 and one Newton step.
@@ -123,7 +116,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
   }
   for (int i = threadIdx.x; i < M; i += blockDim.x) lds_win[i] = v2f{a.window[2 * i], a.window[2 * i + 1]};
   for (int i = threadIdx.x; i < (FP - F) * RS; i += blockDim.x) tile[obj_at(F + (i >> 4), i & 15)] = 0.0f;   // rows the zero-padded filterbank meets
-  OBJ_STAMP(0);
   {
     v2f* twt = reinterpret_cast<v2f*>(uni);                   // W_M^(l*k1), (R-1) x 64 entries: built once, kept in registers
     for (int i = threadIdx.x; i < (R - 1) * 64; i += blockDim.x) {
@@ -138,7 +130,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
 #pragma unroll
   for (int k1 = 1; k1 < R; ++k1) twr.w[k1 - 1] = reinterpret_cast<const v2f*>(uni)[(k1 - 1) * 64 + lane];
   __syncthreads();                                            // (the staging area is the FFT scratch from here on)
-  OBJ_STAMP(1);
 
   // ---- 1. analysis of this wave's two frames ---------------------------------------------------------------------------
   v2f un[2][H], um[2][H], umid[2];
@@ -178,7 +169,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     if (lane == 0) tile[obj_at(M / 2, n)] = amid;
     umid[i] = xmid * (amid > 0.0f ? fast_rcp(amid) : 0.0f);
   }
-  OBJ_STAMP(2);
   constexpr int kRing = 8;
   int n_blk = 1, fe0 = 0, fe1 = 0;
   const int* blk_mg = nullptr;
@@ -213,7 +203,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     dsc_mg = blk_mg[min(fe0 + (lane & (kRing - 1)), n_blk - 1)];
   }
   __syncthreads();
-  OBJ_STAMP(3);
 
   if constexpr (MAG) {
     // ---- 2'-4'. dA = 2/numel (|S| - T) on the tile, squared error; the target is read in the caller's (B, F, T) layout,
@@ -246,7 +235,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
       if (u < a.sp_total) u4[u] = stg[i];
     }
     __syncthreads();
-    OBJ_STAMP(4);
     // ---- 2 + 3 (bands). lane (r, n): mm = row 4 g + r of the filterbank . |S|[:, n] over the row's band, then log1p, squared
     // error and dM in place; dM tile plain [row][frame].  Four bin quads per pass (a band is a multiple of four long); the next
     // pass's operands - the NEXT row quad's first pass after the last one - are requested before this pass's products, so a wave
@@ -310,12 +298,10 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
         q0_cur = q0_nx;
         tv_cur = tv_nx;
       }
-      OBJ_STAMP(5);
       s2 = wave_sum(s2);
       if (lane == 0) lsum[wib] = s2;
     }
     __syncthreads();
-    OBJ_STAMP(6);
     if (threadIdx.x == 0) {
       double tot = 0.0;
       for (int w = 0; w < kObjWaves; ++w) tot += lsum[w];
@@ -409,9 +395,7 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
   for (int i = 0; i < kRing; ++i) av[i] = a.melB[(long long)min(be0 + i, n_blk - 1) * 64 + lane];
   dsc_fg = blk_fg[min(be0 + (lane & (kRing - 1)), n_blk - 1)];
   dsc_mg = blk_mg[min(be0 + (lane & (kRing - 1)), n_blk - 1)];
-  OBJ_STAMP(4);
   __syncthreads();
-  OBJ_STAMP(5);
 
   // ---- 3. V = log1p(mm), squared error, dM = 2/numel (V - T) / (1 + mm) ------------------------------------------------
   {
@@ -434,7 +418,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     if (lane == 0) lsum[wib] = s2;
   }
   __syncthreads();
-  OBJ_STAMP(6);
   if (threadIdx.x == 0) {
     double tot = 0.0;
     for (int w = 0; w < kObjWaves; ++w) tot += lsum[w];
@@ -473,9 +456,7 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     flush(bg1);
   }
   }
-  OBJ_STAMP(7);
   __syncthreads();
-  OBJ_STAMP(8);
 
   // ---- 5. gradient frames: G = dA S/|S| (Hermitian weights), inverse FFT, window --------------------------------------------
   v2f fr[2][R];
@@ -513,9 +494,7 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
 #pragma unroll
     for (int u = 0; u < R; ++u) fr[i][u] = z[u] * lds_win[64 * u + lane];
   }
-  OBJ_STAMP(9);
   __syncthreads();                                            // every inverse transform is done: the scratch becomes the span
-  OBJ_STAMP(10);
 
   // ---- 6. overlap-add: the windowed frames go to LDS (the |S| / dA tile, the dM tile and the scratch are one region of
   // >= 16 n_fft floats, all free by now), then every output sample gathers what covers it, in frame order.  With hop = n_fft/2,
@@ -550,7 +529,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     }
   }
   __syncthreads();
-  OBJ_STAMP(11);
   // units of the gather: frames (step hop, length n_fft) or pair sums (step 2 hop, length n_fft + hop)
   const int ulen = pairs ? N + a.hop : N, ustep = pairs ? 2 * a.hop : a.hop, ush = pairs ? 1 : 0;
   const int ulast = pairs ? (nfr - 1) >> 1 : nfr - 1;
@@ -653,7 +631,6 @@ __global__ __launch_bounds__(64 * kObjWaves, 2) void k_objective_logmel(ObjArgs 
     // remainder) take no part in the objective: zero gradient
     for (long long nn = n0 + span_len + threadIdx.x; nn < a.len; nn += blockDim.x) go[nn] = 0.0f;
   }
-  OBJ_STAMP(12);
 }
 
 

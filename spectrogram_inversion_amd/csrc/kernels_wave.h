@@ -24,11 +24,6 @@
 
 #include "wave_api.h"
 
-
-#ifndef SPECINV_WAVE_OLA_ALL        // experiments: 1 the register overlap-add for float64 frames of 16 points per lane as well
-#define SPECINV_WAVE_OLA_ALL 0
-#endif
-
 namespace specinv {
 namespace wave {
 
@@ -295,24 +290,17 @@ constexpr int max_threads() { return (sizeof(T) == 8 && m_of<LOGM>() / Geo<T, LO
 // ... and with the ring (measured at 4 / 3 / 2 waves per SIMD, tools/log/EXPERIMENTS.md r06-u: float64 512 / 300 / 100 0.499 / 0.397 /
 // 0.398 ms, 1024 / 800 / 200 0.513 / 0.351 / 0.247, 256 / 200 / 50 0.754 / 0.529 / 0.471 - at 128 registers those spill 31 ... 280;
 // float32 1024 / 800 / 200 0.295 / 0.260 / 0.286, 256 / 200 / 50 0.304 / 0.272 / 0.301)
-#ifndef SPECINV_WAVE_RING_WPS64
-#define SPECINV_WAVE_RING_WPS64 2
-#endif
-#ifndef SPECINV_WAVE_RING_WPS32
-#define SPECINV_WAVE_RING_WPS32 3
-#endif
+constexpr int kRingWavesF64 = 2, kRingWavesF32 = 3;
 // ... at n_fft 400 / 800 / 1000 (ten points per lane; 3 / 2 waves per SIMD: 1000 / 250 0.111 / 0.084 ms, ADMM 400 / 100 0.430 / 0.313,
 // 400 / 160 0.277 / 0.272, 800 / 200 0.329 / 0.336)
-#ifndef SPECINV_WAVE_RING_WPS32S
-#define SPECINV_WAVE_RING_WPS32S 2
-#endif
+constexpr int kRingWavesF32Ten = 2;
 template <typename T, int LOGM, int OV, bool TWO>
 constexpr int waves_per_simd() {
   if (Geo<T, LOGM>::LG > 64) return 2;            // (a team's workgroups: four to a CU by their LDS)
   // (the ring: a wave's frame buffers and rings are 16 KB of LDS where a lane carries 16 points - two waves per SIMD fit anyway)
   if (OV == 1 && sizeof(T) == 4 && m_of<LOGM>() / Geo<T, LOGM>::LG >= 16) return 2;
   if (TWO) return sizeof(T) == 8 || LOGM >= 100 ? 2 : 3;
-  if (OV == 1) return sizeof(T) == 8 ? SPECINV_WAVE_RING_WPS64 : (LOGM >= 100 ? SPECINV_WAVE_RING_WPS32S : SPECINV_WAVE_RING_WPS32);
+  if (OV == 1) return sizeof(T) == 8 ? kRingWavesF64 : (LOGM >= 100 ? kRingWavesF32Ten : kRingWavesF32);
   return max_threads<T, LOGM>() == 512 ? 2 : (OV > 1 ? ((m_of<LOGM>() / Geo<T, LOGM>::LG >= 16 || sizeof(T) == 8) ? 2 : 3) : 4);
 }
 
@@ -774,7 +762,7 @@ constexpr bool ola_fits() {
   // (the sizes that are not powers of two: the ring only)
   // (... and float32 n_fft 16384 at hop = n_fft / 8: seven blocks of sums beside sixteen points - 0.394 ms against 0.270 on frames + k_ola)
   if (LOGM == 13 && OV == 8) return false;
-  return OV <= 1 || (LOGM < 100 && (SPECINV_WAVE_OLA_ALL || !(sizeof(T) == 8 && m_of<LOGM>() / G::LG >= 16)) &&
+  return OV <= 1 || (LOGM < 100 && !(sizeof(T) == 8 && m_of<LOGM>() / G::LG >= 16) &&
                      (G::NPASS == 4 ? G::R3 : G::NPASS == 3 ? G::R2 : G::R1) % OV == 0);
 }
 
@@ -844,9 +832,6 @@ Launch shape(int64_t work, int mode, int ov) {
       if (LOGM < 100 && w != 4 && w != 8) continue;
       if (TEAM > 1) w = TEAM;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * w, lds_of(w)) != hipSuccess) nb = 0;
-      if (const char* e = getenv("SPECINV_WAVE_WPW")) {
-        if (TEAM == 1 && atoi(e) != w) continue;
-      }
       if (nb * w > best) {
         best = nb * w;
         wpw_of[key] = w;

@@ -10,13 +10,6 @@ namespace fast {
 
 using f32x4 = float __attribute__((ext_vector_type(4)));
 
-#ifndef SPECINV_OBJ_STAMPS        // diagnostic build: s_memtime at the phase boundaries of one wave of every workgroup
-#define SPECINV_OBJ_STAMPS 0      // (tools/obj_stamps.py; the shipped kernel executes no stamp)
-#endif
-#ifndef SPECINV_OBJ_STAMP_WAVE    // ... which wave (0 .. 7; 0 - 3 are the older waves of their SIMDs, 4 - 7 the younger ones)
-#define SPECINV_OBJ_STAMP_WAVE 0
-#endif
-
 constexpr int kObjWaves = 8;      // waves per workgroup
 constexpr int kObjTile = 16;      // frames per tile (the N of the MFMA), two per wave
 constexpr int kObjRow = 16;       // floats per row of the [bin][frame] tiles; elements sit at obj_at(row, frame)
@@ -58,9 +51,6 @@ struct ObjArgs {
   const int* ctl_eval;
   const int* ctl_cur;
   float* grad_alt;
-#if SPECINV_OBJ_STAMPS
-  unsigned long long* stamps;   // [tiles][16]
-#endif
 };
 
 // what lbfgs_dev.h hands to the objective: the gate and the gradient ping-pong of the optimiser's state record; for the frame walk

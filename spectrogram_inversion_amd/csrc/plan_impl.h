@@ -219,7 +219,7 @@ struct PlanT final : PlanBase {
     fc.maxb = 0;
     lds_bytes2 = 2 * (size_t)nf * sizeof(C);         // two buffers: every kernel can run (RTISI-LA and the L-BFGS chain need them)
     // In-place transforms (kernels_generic.h: FrameCfg::inplace) for k_stft / k_iter_pair / k_grad_frames: one buffer - more
-    // workgroups per CU for a latency-bound kernel (measured, tools/bench_generic_r04.py: float64 2048 / 512 0.58 -> 0.44 ms per
+    // workgroups per CU for a latency-bound kernel (measured, tools/log/EXPERIMENTS.md r04 f, g, h: float64 2048 / 512 0.58 -> 0.44 ms per
     // iteration, float64 512 two-sided 1.40 -> 1.02, float32 8192 0.64 -> 0.31; float32 at n_fft <= 1024 2 % slower: the extra
     // barrier per stage with nothing to gain) - and the only form beyond n_fft 8192 (float32) / 4096 (float64).
     bool ip_ok = true;
@@ -240,8 +240,7 @@ struct PlanT final : PlanBase {
       while (ip_threads < 1024 && !fits(ip_threads)) ip_threads *= 2;
       ip_ok = fits(ip_threads);
     }
-    const char* ip_env = getenv("SPECINV_GENERIC_INPLACE");           // (experiments: 0 never, 1 whenever possible)
-    use_inplace = ip_ok && (sizeof(T) == 8 || lds_bytes2 > 16 * 1024 || (ip_env && ip_env[0] == '1')) && !(ip_env && ip_env[0] == '0');
+    use_inplace = ip_ok && (sizeof(T) == 8 || lds_bytes2 > 16 * 1024);
     lds_bytes = use_inplace ? lds_bytes2 / 2 : lds_bytes2;
     SI_CHECK(lds_bytes <= 160 * 1024 - 256, SPECINV_EUNSUPPORTED,
              "n_fft=%d needs %zu bytes of LDS per frame (limit 160 KiB)", n, lds_bytes);
@@ -286,15 +285,14 @@ struct PlanT final : PlanBase {
         dr_threads = std::min(256, std::max(64, n / 4 / 64 * 64));
         while (dr_threads < 1024 && n / 8 > dr_threads * per_trip * 2) dr_threads *= 2;
       }
-      if (const char* e2 = getenv("SPECINV_GENERIC_DR_THREADS")) dr_threads = std::max(64, std::min(1024, atoi(e2) / 64 * 64));
       const char* dr_env = getenv("SPECINV_GENERIC_DR");          // (experiments / tests: 0 keeps the Stockham kernels)
-      // where it wins (round 5, tools/bench_generic_r05.py, one box): float64 n_fft 1024 / 2048 -10 ... -13 %, float32 n_fft 2048
+      // where it wins (round 5, tools/log/EXPERIMENTS.md r05 j - q, one box): float64 n_fft 1024 / 2048 -10 ... -13 %, float32 n_fft 2048
       // (two-sided) -32 %; float64 512 +-3 %, float64 4096 +12 %, float32 <= 1024 +2 ... +5 %, n_fft >= 8192 +2 ... +20 %: those
       // keep the Stockham kernels (SPECINV_GENERIC_DR=1 forces this one wherever it fits)
       const bool wins = sizeof(T) == 8 ? (n == 1024 || n == 2048) : n == 2048;
       use_dr = dr_lds <= 160 * 1024 - 256 && !(dr_env && dr_env[0] == '0') && (wins || (dr_env && dr_env[0] == '1'));
     }
-    // Power-of-two n_fft 128 ... 2048: the wave-level coverage kernel (kernels_wave.h, round 6) - float64 at every size it covers,
+    // n_fft 128 ... 8192 (powers of two), 400 / 800 / 1000 and float32 16384: the wave-level coverage kernel (kernels_wave.h, round 6) - float64 at every size it covers,
     // float32 at n_fft 128 / 256 (512 ... 4096 have the packed wave-level kernels of fast_core.h; what falls through those - a
     // two-sided run that keeps X and U - stays on k_iter_pair).  SPECINV_GENERIC_WAVE=0 never, =1 wherever it covers.
     {
@@ -776,13 +774,12 @@ struct PlanT final : PlanBase {
           continue;
         }
         const dim3 grid((Tn() + 1) / 2, B()), blk(use_dr ? dr_threads : frame_threads());   // two frames per complex FFT
-        static const bool ip_small = !(getenv("SPECINV_GENERIC_IP256") && getenv("SPECINV_GENERIC_IP256")[0] == '0');
         {
           const void* fn = nullptr;
           const int mode = method == Method::Gla ? 0 : 1;
           if (use_dr) fn = mode == 0 ? (ev ? (const void*)k_iter_pair_dr<T, 0, true> : (const void*)k_iter_pair_dr<T, 0, false>)
                                      : (ev ? (const void*)k_iter_pair_dr<T, 1, true> : (const void*)k_iter_pair_dr<T, 1, false>);
-          else if (use_inplace && blk.x <= 256 && ip_small)
+          else if (use_inplace && blk.x <= 256)
             fn = mode == 0 ? (ev ? (const void*)k_iter_pair<T, 0, true, true, 256> : (const void*)k_iter_pair<T, 0, false, true, 256>)
                            : (ev ? (const void*)k_iter_pair<T, 1, true, true, 256> : (const void*)k_iter_pair<T, 1, false, true, 256>);
           else if (use_inplace) fn = mode == 0 ? (ev ? (const void*)k_iter_pair<T, 0, true, true> : (const void*)k_iter_pair<T, 0, false, true>)

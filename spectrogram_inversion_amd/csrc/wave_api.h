@@ -1,5 +1,5 @@
-// Host interface of the wave-level coverage kernel (kernels_wave.h, compiled in tu_wave.hip): one Griffin-Lim / ADMM iteration's
-// frame part - torch_specinv/methods.py:241-248, :464-477 - for float32 AND float64 at power-of-two n_fft 128 ... 2048, any hop,
+// Host interface of the wave-level coverage kernel (kernels_wave.h, compiled in the tu_wave_*.hip units): one Griffin-Lim / ADMM iteration's
+// frame part - torch_specinv/methods.py:241-248, :464-477 - for float32 AND float64 at n_fft 128 ... 8192 (powers of two), 400 / 800 / 1000 and float32 16384, any hop,
 // centring, pad mode, sidedness and `normalized`, on the coverage path's buffers (x, the (B, T, F) state and target, the frames
 // that k_ola overlap-adds): what k_iter_pair / k_iter_pair_dr compute, on a transform that lives in a wave instead of a workgroup.
 #pragma once
@@ -27,7 +27,7 @@ struct WaveIterArgs {
   int nch = 0, ov = 0;      // chunks of frames per item; wave_iter_ola_chunks' ov_out (0: frames buffer + k_ola)
 };
 
-// n_fft the kernel covers (a power of two, 128 ... 2048)
+// n_fft the kernel covers (tu_wave_f32.hip)
 bool wave_iter_covers(int n_fft, int elem_size);
 // ... and the frame counts its 32-bit frame indices and row offsets take (`chunks`: with the register overlap-add, whose lane groups
 // walk chunks up to n_frames apart); beyond them the plan uses the frames form / the workgroup-level kernels

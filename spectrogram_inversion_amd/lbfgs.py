@@ -161,7 +161,7 @@ class LBFGS:
         self.d = None
         self.t = None
         # the recursion on Gram matrices (two passes over the memory) needs the one-pass vector kernels
-        self.gram = hasattr(self.ops, "multi_dot") and hasattr(self.ops, "lincomb") and os.environ.get("SPECINV_LBFGS_GRAM", "1") != "0"
+        self.gram = hasattr(self.ops, "multi_dot") and hasattr(self.ops, "lincomb")
         self._forget()
         self.prev_grad = None
         self.prev_loss = None

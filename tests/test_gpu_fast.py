@@ -62,7 +62,7 @@ def test_fast_path_selected_and_matches_oracle(n_fft, hop, frames, batch, chunk)
         assert done == 10 and len(evals) == 2
         y = N(plan.wave())
         # gate = the north-star bar (waveform rel-L2 <= 1e-4); typical value 1e-6..2e-5, the 6-frame case
-        # amplifies float32 rounding noise ~200x in 10 iterations for any kernel (tools/acc_small.py)
+        # amplifies float32 rounding noise ~200x in 10 iterations for any kernel
         assert rel_l2(y, ref.reshape(y.shape)) < 1e-4, (keep, rel_l2(y, ref.reshape(y.shape)))
         got = sc_linear(np.array([m for _, m, _ in evals]))
         want = sc_linear(np.array([m for _, m, _ in trace]))
@@ -556,7 +556,7 @@ def test_time_domain_momentum_against_spectral_state(n_fft, batch, frames, ov, a
     STFT, methods.py:243-244) against `k_fused4` iterating on pre_spec itself, same input: 40 iterations with evaluations in the
     phase where the c0 term is still added (iteration 3), around the switch and after it; small launches and the C2 geometry.
     The two differ only in where the linear combination is rounded (alpha = 0: the same operations); metric sums to
-    1e-5 relative, waveforms by the segment statistics below (`tools/td_study2.py` prints them per seed).  Every overlap
+    1e-5 relative, waveforms by the segment statistics below.  Every overlap
     (hop = n_fft/2, /4, /8) and transform size of the fused path."""
     hop = n_fft // ov
     tuned = ov == 4 and n_fft in (1024, 2048)

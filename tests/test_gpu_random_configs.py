@@ -56,8 +56,8 @@ def draw(seed, wave_level=False):
 
 # SPECINV_EXTRA_SEEDS="a:b" adds seeds a..b-1 (even: the full draw, odd: wave-level shapes) for an occasional wider sweep
 # (1000:1800 -> 905 pass; 1291, a rectangular win_length < n_fft window with hop = n_fft/2, is ill-conditioned at the
-# signal's end: every kernel path AND the float32 oracle leave the float64 oracle by 2e-2 there after 3 iterations,
-# tools/dbg_seed.py 1291; round 6, 1000:1800 -> 1732 pass: 1291 again and three RTISI draws with hop > n_fft / 2 - 1012, 1141, 1168 -
+# signal's end: every kernel path AND the float32 oracle leave the float64 oracle by 2e-2 there after 3 iterations;
+# round 6, 1000:1800 -> 1732 pass: 1291 again and three RTISI draws with hop > n_fft / 2 - 1012, 1141, 1168 -
 # where the float32 oracle itself is 2e-3 from the float64 one and the kernel 2 - 2.5 x that, over the 2 x bar)
 _extra = os.environ.get("SPECINV_EXTRA_SEEDS", "")
 EXTRA = list(range(*map(int, _extra.split(":")))) if _extra else []

@@ -98,7 +98,7 @@ def test_semi_equals_generic(n_fft, hop, frames, batch, extra):
         s = p.iterate(1, eval_last=True)
         out.append((N(p.wave()), s, N(p.state_spec(0))))
     # (a handful of frames leave the edges with a tiny envelope: float32 rounding noise is amplified
-    # ~10x per iteration by any two implementations, tools/acc_small.py)
+    # ~10x per iteration by any two implementations)
     tol = 5e-4 if frames <= 5 else 5e-5
     assert rel_l2(out[0][0], out[1][0]) < tol
     np.testing.assert_allclose(out[0][1], out[1][1], rtol=2e-5)
@@ -246,7 +246,7 @@ def test_chunked_frame_kernel_many_chunks_long_signal(chunked_kernel):
 
 # SPECINV_EXTRA_SEEDS="a:b": more seeds for an occasional wider sweep (1000:1600 -> 595 of 600 within the tolerance; the
 # others hold one of Griffin-Lim's local chaotic events - a bin passing close to zero - where k_hop, k_semi and the
-# float32 oracle all leave the float64 oracle by 1e-4 ... 1e-3 in the same three hop-blocks, tools/dbg_hop_seed.py)
+# float32 oracle all leave the float64 oracle by 1e-4 ... 1e-3 in the same three hop-blocks)
 _extra = os.environ.get("SPECINV_EXTRA_SEEDS", "")
 EXTRA = list(range(*map(int, _extra.split(":")))) if _extra else []
 

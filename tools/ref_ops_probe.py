@@ -9,8 +9,8 @@ Findings (torch 2.10.0 CPU, AVX512 build; 2^22 random bins):
   * y / envelope (methods.py:132, real tensors) is an IEEE division.
 Candidates (emulated in float64 -> float32 here; the kernels' forms are in csrc/fast_core.h):
   A  r02/r03 "exact" build:  RN(x m / (RN sqrt(fma(x,x,y y)) + 1e-16))             (IEEE sqrt + division of the product)
-  B  SPECINV_REFCHAIN=1:     (x m) * RN(1 / (RN sqrt(t) + 1e-16)),  t = fma(x,x,fl(y y))
-  C  SPECINV_REFCHAIN=2:     (x m) * RN(t^-1/2)                       one rounding of the exact inverse root
+  B  both roundings:         (x m) * RN(1 / (RN sqrt(t) + 1e-16)),  t = fma(x,x,fl(y y))
+  C  the kernels' chain:     (x m) * RN(t^-1/2)                       one rounding of the exact inverse root
   D  default approximations:  x * (m * rsq(t)),  rsq good to 1 ulp (emulated as the correctly rounded value: a best case)
 """
 import numpy as np
@@ -47,7 +47,7 @@ def ulp(a, b):
 
 exact = x.astype(np.float64) * m.astype(np.float64) / np.sqrt(x.astype(np.float64) ** 2 + y.astype(np.float64) ** 2)
 print(f"{'':28s} bit-identical   mean ulp   rms rel. deviation from the reference's value | from the exact value")
-for name, o in (("reference chain itself", ref), ("A  IEEE sqrt + division", A), ("B  REFCHAIN=1", B), ("C  REFCHAIN=2", C), ("D  default (ideal rsq)", D)):
+for name, o in (("reference chain itself", ref), ("A  IEEE sqrt + division", A), ("B  both roundings", B), ("C  kernels' chain", C), ("D  default (ideal rsq)", D)):
     dev = np.sqrt(np.mean(((o.astype(np.float64) - ref) / np.maximum(np.abs(ref), 1e-30)) ** 2))
     dex = np.sqrt(np.mean(((o.astype(np.float64) - exact) / np.maximum(np.abs(exact), 1e-30)) ** 2))
     print(f"{name:28s} {(o == ref).mean():10.4f} {ulp(o, ref).mean():10.3f}   {dev:.2e} | {dex:.2e}")
