@@ -78,9 +78,8 @@ typedef int (*specinv_eval_cb)(const specinv_eval* ev, void* user);
 
 const char* specinv_last_error(void);
 int specinv_abi_version(void);
-/* 1 if the library carries the approximate-projection copies of the float32 wave-level kernels (built with SPECINV_BUILD_APPROX=1;
- * not in a default build since round 6: five translation units, ~2 CPU-minutes, for a 3 % opt-in), else 0 - specinv_plan_set_exact(plan, 0)
- * is then accepted and the plan keeps the reference's operation order. */
+/* Kept for compatibility: always 0.  The library carries no approximate-projection kernels; the reference's operation order
+ * (specinv_plan_set_exact) is its only arithmetic. */
 int specinv_has_approx(void);
 
 /* ---- plan ---------------------------------------------------------------------------- */
@@ -109,15 +108,12 @@ int64_t specinv_plan_device_bytes(const specinv_plan* plan);
 int specinv_plan_launch_geometry(const specinv_plan* plan, int32_t out[4]);
 /* 0: allow the fast path when the configuration supports it (default); 1: force the generic kernels. */
 int specinv_plan_force_generic(specinv_plan* plan, int on);
-/* The arithmetic of the magnitude projection S * m / (|S| + 1e-16) and of the division by the overlap-add envelope
- * (torch_specinv/methods.py:132,246-247) on the float32 wave-level kernels (fused, frame, chunked frame).
- * on = 1 (the default since round 4): the reference's operation order - ATen executes the projection as (S * m) * r with r the rounded
- * reciprocal of |S| + 1e-16 (tools/ref_ops_probe.py) - with r the correctly rounded 1 / |S| (one Newton step on v_rsq_f32) and a
- * correctly rounded division by the envelope: 73 % of the projected bins bit-identical to the reference's chain, every one within
- * its rounding noise; + 3 % on the headline step.  on = 0: S * (m * v_rsq_f32(|S|^2 + 1e-32)) and a multiplication by 1 / envelope
- * (52 % bit-identical, the same distance from the exact value).  The generic kernels and float64 use IEEE operations in the
- * reference's order throughout.  Takes effect at the next specinv_gla_init / specinv_admm_init.  on = 0 needs a library built with
- * SPECINV_BUILD_APPROX=1 (specinv_has_approx()); a default build keeps on = 1 whatever is asked. */
+/* Kept for compatibility: checks the plan and returns SPECINV_OK, whatever `on` is.  The float32 wave-level kernels (fused, frame,
+ * chunked frame) always compute the magnitude projection S * m / (|S| + 1e-16) and the division by the overlap-add envelope
+ * (torch_specinv/methods.py:132,246-247) in the reference's operation order - ATen executes the projection as (S * m) * r with r
+ * the rounded reciprocal of |S| + 1e-16 (tools/ref_ops_probe.py) - with r the correctly rounded 1 / |S| (one Newton step on
+ * v_rsq_f32) and a correctly rounded division by the envelope: 73 % of the projected bins bit-identical to the reference's chain,
+ * every one within its rounding noise.  The generic kernels and float64 use IEEE operations in the reference's order throughout. */
 int specinv_plan_set_exact(specinv_plan* plan, int on);
 /* The float32 fast paths do not carry the reference's spectral state as such.
  * ADMM keeps only Y = X + U between iterations: methods.py:467-468 read the two as U + X, i.e. the Y that :475 has just

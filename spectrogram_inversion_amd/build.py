@@ -6,8 +6,6 @@ hipcc cross-compiles without a GPU; the resulting .so sits next to the sources
 (spectrogram_inversion_amd/libspecinv.so), is git-ignored and travels to the GPU
 box with the repo snapshot.
 
-    SPECINV_BUILD_APPROX=1 python -m spectrogram_inversion_amd.build      (+ the approximate-projection kernels, see with_approx)
-
 The library is two dozen translation units (csrc/*.hip): the plan and the light kernels in
 specinv.hip, each family of heavy wave-level kernels in its own tu_*.hip (explicit
 instantiations), compiled in parallel and linked once.  Objects and their dependency
@@ -42,17 +40,8 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or add /opt/rocm/bin to PATH)")
 
 
-def with_approx() -> bool:
-    """SPECINV_BUILD_APPROX=1: also build the approximate-projection copies of the float32 wave-level kernels (tu_approx_*.hip - five
-    units that compile every kernel header a second time, ~2 CPU-minutes - selected per plan by specinv_plan_set_exact(plan, 0): 3 %
-    on the headline step, used by no BASELINE configuration).  Default: not built; tu_noapprox.hip stands in with empty kernel tables."""
-    return os.environ.get("SPECINV_BUILD_APPROX", "0") == "1"
-
-
 def sources():
-    names = [f for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
-    names = [f for f in names if (f != "tu_noapprox.hip" if with_approx() else not f.startswith("tu_approx_"))]
-    srcs = [os.path.join(CSRC, f) for f in names]
+    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
     hdrs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     hdrs.append(os.path.join(os.path.dirname(PKG_DIR), "include", "specinv.h"))
     return srcs, hdrs
@@ -81,7 +70,7 @@ def is_stale() -> bool:
     srcs, hdrs = sources()
     if any(os.path.getmtime(p) > t for p in srcs + hdrs):
         return True
-    try:                                            # (the set of units linked last time: SPECINV_BUILD_APPROX toggled since?)
+    try:                                            # (the set of units linked last time: a unit added or removed since?)
         with open(_units_stamp()) as fh:
             return fh.read().split() != [os.path.basename(p) for p in srcs]
     except OSError:

@@ -38,22 +38,12 @@
 #include "common.h"
 #include "kernels_generic.h"
 
-#ifndef SPECINV_IEEE        // 1 (default): the reference's operation order in the projection, (s m) r with r the correctly rounded
-#define SPECINV_IEEE 1      //    1 / |s|, and a true division by the envelope (methods.py:132,246-247; ref_rcp_abs2 below);
-#endif                      // 0: s (m v_rsq_f32(|s|^2 + 1e-32)) and a multiplication by 1 / envelope (the fast_approx copy)
-
-// The wave-level kernels are compiled twice: as `specinv::fast` with the reference's operation order and correctly rounded factors
-// (SPECINV_IEEE=1, the default arithmetic since round 4: + 3 % on the headline step, tools/refchain_study.py), and - in the
-// tu_approx_*.hip units, which define SPECINV_IEEE=0 and SI_FAST_NS=fast_approx before including the kernel headers - as
-// `specinv::fast_approx` with the hardware's approximate inverse square root in the projection and a multiplication by
-// 1 / envelope.  `specinv_plan_set_exact(plan, 0)` selects the second set (fast_state.h takes its kernels' addresses from the
-// extern "C" tables of those units).
-#ifndef SI_FAST_NS
-#define SI_FAST_NS fast
-#endif
+// The wave-level kernels have one arithmetic: the reference's operation order in the projection, (s m) r with r the correctly
+// rounded 1 / |s|, and a true division by the envelope (methods.py:132,246-247; ref_rcp_abs2 below).  It has been the default since
+// round 4, at + 3 % on the headline step over the approximate projection that it replaced (profiles/r04_refchain.txt).
 
 namespace specinv {
-namespace SI_FAST_NS {
+namespace fast {
 
 // Launch shapes that the kernels' __launch_bounds__ and the host's launch setup (fast_state.h) agree on (tools/log/EXPERIMENTS.md)
 constexpr int kMinWaves = 2;       // waves per SIMD of the wave-level kernels (caps the register allocation)
@@ -719,7 +709,7 @@ struct FastArgs {
   const v4f* m_pairs;  // target magnitude                          [B*T][H/2][64] x (k_2c, M-k_2c, k_2c+1, M-k_2c+1)
   const float* m_mid;  //                                           [B*T]
   const float* window;   // N
-  const float* inv_env;  // L, 1 / envelope
+  const float* env;      // L, the envelope
   double* partials;      // [n_waves][2]
   int T, nchunks, n_waves, pad_mode;
   long long L;
@@ -742,7 +732,6 @@ struct FastArgs {
 // |s| where only the metric reads it (sums compared to 1e-5: the hardware square root is good to 1 ulp)
 __device__ __forceinline__ float fast_abs(v2f s) { return __builtin_amdgcn_sqrtf(fmaf(s.x, s.x, s.y * s.y)); }
 __device__ __forceinline__ float fast_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
-#if SPECINV_IEEE
 // ---- the reference's operation order from corrected hardware approximations ------------------------------------------------
 // methods.py:246-247 is `spec * target / (spec.abs() + 1e-16)`.  What ATen executes for it (torch 2.10 CPU, checked value by
 // value on 2^22 random bins, tools/ref_ops_probe.py): abs = hypotf (correctly rounded), and the complex / real division is a
@@ -753,9 +742,9 @@ __device__ __forceinline__ float fast_rcp(float v) { return __builtin_amdgcn_rcp
 // its reciprocal): two transcendental and four packed instructions per PAIR of bins, no division; 73 % of the outputs bit-identical
 // to the reference's chain, rms deviation from it 4.9e-8 relative - and from the EXACT value 4.7e-8, where the reference's own
 // chain has 5.1e-8.  A chain with both of the reference's roundings (88 % bit-identical) cost + 5.3 % on the BASELINE C2 step
-// against + 3.1 % (tools/refchain_study.py, profiles/r04_refchain.txt).
+// against + 3.1 % (profiles/r04_refchain.txt).
 // For comparison: the IEEE sqrt + two divisions of rounds 2-3 (x m / d: not the reference's chain) matched 65 % at + 27 %, the
-// approximate path (SPECINV_IEEE=0: s (m rsq(t))) 52 %; every form sits 4.7-5.3e-8 from the exact value.
+// approximate path (s (m rsq(t)), retired) 52 %; every form sits 4.7-5.3e-8 from the exact value.
 // kRefFloor keeps rsq finite at s = 0 (then out = 0 like the reference's 0 / 1e-16) and bounds r by 1e16 like the guard does; it
 // is absorbed by t above |s| = 6e-13 (the chain has no other guard: it only differs from the reference's below |s| = 3e-9).
 constexpr float kRefFloor = 1e-32f;
@@ -785,19 +774,6 @@ __device__ __forceinline__ v2f env_apply_r(v2f v, v2f e, v2f r) {
 }
 __device__ __forceinline__ v2f env_apply(v2f v, v2f e) { return v2f{__fdiv_rn(v.x, e.x), __fdiv_rn(v.y, e.y)}; }
 __device__ __forceinline__ float env_apply(float v, float e) { return __fdiv_rn(v, e); }
-#else
-// the envelope table holds 1 / envelope
-__device__ __forceinline__ v2f env_rcp(v2f e) { return e; }
-__device__ __forceinline__ v2f env_apply_r(v2f v, v2f e, v2f) { return v * e; }
-__device__ __forceinline__ v2f env_apply(v2f v, v2f e) { return v * e; }
-__device__ __forceinline__ float env_apply(float v, float e) { return v * e; }
-#endif
-
-// The projection's factor m / (|s| + 1e-16) (methods.py:246-247) on the default (approximate) path: m * rsq(|s|^2 + 1e-32) -
-// one transcendental instruction instead of two (they cost two issue slots each) and no addition.  v_rsq_f32 is good to 1 ulp like
-// v_sqrt_f32 and v_rcp_f32 each; the guard term only matters below |s| ~ 1e-9, where both forms tend to m * 1e16, and s = 0 gives
-// 0 either way.  The exact-projection build (SPECINV_IEEE) keeps the reference's operations.
-__device__ __forceinline__ float proj_rsq(v2f s) { return __builtin_amdgcn_rsqf(fmaf(s.y, s.y, fmaf(s.x, s.x, 1e-32f))); }
 
 // Frequency-domain update of one bin.  `r` is the STFT bin, `p`/`u` the stored state, `m` the target.
 // Returns the bin to synthesise from (already multiplied by isc); writes the new state.
@@ -816,28 +792,17 @@ __device__ __forceinline__ v2f update_bin(v2f r, v2f& p, v2f& u, v2f& xs, float 
     // methods.py:243-247: S = R - lr*P ; P <- S ; S * m / (|S| + 1e-16)
     const v2f s = v2f{fmaf(-a.coef, p.x, r.x), fmaf(-a.coef, p.y, r.y)};
     p = s;
-#if SPECINV_IEEE
     return ((s * m) * ref_rcp_abs(ref_norm2(s))) * a.inv_scale;
-#else
-    return s * ((m * proj_rsq(s)) * a.inv_scale);
-#endif
   } else {
     // methods.py:467-475 with p = Y of the previous iteration (= fl(X + U), the first operation of :468)
     const v2f y = p;
     const v2f z = v2f{fmaf(a.coef, y.x, r.x) * a.inv1p, fmaf(a.coef, y.y, r.y) * a.inv1p};
     const v2f un = y - z;
     v2f xn = z - un;
-#if SPECINV_IEEE
     {
 #pragma clang fp contract(off)   // X is rounded before Y = X + U is formed (:473-475): no multiply-add across the two
       xn = (xn * m) * ref_rcp_abs(ref_norm2(xn));
     }
-#else
-    {
-#pragma clang fp contract(off)   // X is rounded before Y = X + U is formed (:473-475): no multiply-add across the two
-      xn = xn * (m * proj_rsq(xn));
-    }
-#endif
     xs = xn;
     u = un;
     p = xn + un;
@@ -1117,5 +1082,5 @@ __global__ void k_hop_td(HopArgs s);
 template <int R>
 __global__ void k_hop_inverse(HopInvArgs a);
 
-}  // namespace SI_FAST_NS (fast, or fast_approx in the approximate-projection units)
+}  // namespace fast
 }  // namespace specinv

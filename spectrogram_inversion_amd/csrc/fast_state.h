@@ -4,24 +4,7 @@
 #include "fast_core.h"
 #include "kernels_layout.h"
 
-// kernel tables of the approximate-projection units (tu_approx_*.hip): nullptr where there is no such kernel
-extern "C" {
-__attribute__((visibility("hidden"))) const void* specinv_approx_fused_a(int R, int OV, int mode, int eval, int tuned4);
-__attribute__((visibility("hidden"))) const void* specinv_approx_fused_b(int R, int OV, int mode, int eval, int tuned4);
-__attribute__((visibility("hidden"))) const void* specinv_approx_fused_c(int R, int OV, int mode, int eval, int tuned4);
-__attribute__((visibility("hidden"))) const void* specinv_approx_td(int R, int OV, int early, int eval, int tuned4);
-__attribute__((visibility("hidden"))) const void* specinv_approx_frame(int family, int R, int a, int b);
-__attribute__((visibility("hidden"))) int specinv_approx_units_built(void);   // 0: the library was built without them (tu_noapprox.hip)
-}
-
 namespace specinv {
-
-inline const void* approx_fused(int R, int OV, int mode, int eval, int tuned4) {
-  const void* fn = specinv_approx_fused_a(R, OV, mode, eval, tuned4);
-  if (!fn) fn = specinv_approx_fused_b(R, OV, mode, eval, tuned4);
-  if (!fn) fn = specinv_approx_fused_c(R, OV, mode, eval, tuned4);
-  return fn;
-}
 
 // ---- host side ---------------------------------------------------------------------------------------
 struct FastBuf {
@@ -62,7 +45,6 @@ struct FastState {
   bool xform_ok = false;
   bool two = false;
   bool keep_state = false;
-  bool exact = true;
   int n_partials = 0;
   int setup(const specinv_stft_cfg&, const std::vector<T>&, int64_t, int) { return SPECINV_OK; }
   void geometry(int out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
@@ -108,7 +90,7 @@ struct FastState<float> {
   int skew = 0;        // frames every odd chunk cedes to the even chunk before it (chunk_begin; set per Griffin-Lim run in begin_t)
   int cur = 0;   // index of the buffers holding the current state
   int mode = fast::MODE_GLA;
-  FastBuf xb[2], xtail[2], Pb[2], Pmid[2], mpairs, mmid, inv_env, scratch;
+  FastBuf xb[2], xtail[2], Pb[2], Pmid[2], mpairs, mmid, scratch;
   // a two-sided spectrogram (onesided=False): the frame kernel k_semi2 with the mirror bins' state and target beside the lower
   // half's (FastArgs::P2_out); no fused / chunked / signal-form kernels, no stand-alone transforms
   bool two = false;
@@ -116,10 +98,6 @@ struct FastState<float> {
   // ADMM carries Y = X + U in Pb (FastArgs).  X and U themselves are only written when the caller has asked for them
   // (specinv_plan_keep_state), by the last iteration of every iterate() call.
   bool keep_state = false, xu_valid = false;
-  // the projection in the reference's operation order with correctly rounded factors and a true division by the envelope (the
-  // default kernels); false: the approximate copies of the tu_approx_*.hip units, 3 % faster on the headline step
-  // (specinv_plan_set_exact)
-  bool exact = true;
   FastBuf Xb, Xmid, Ub, Umid;
   // Griffin-Lim on k_fused4_td: the momentum state is the signal z (zb), Pb keeps the starting spectrum c0
   bool td = false;
@@ -318,10 +296,9 @@ struct FastState<float> {
     mode = md;
     // (n_fft 4096 runs one wave per SIMD: its vector latency, not the state traffic, is what bounds it there - the signal form
     // measured 0.360 against 0.340 ms per iteration and is not used)
-    if (two || !specinv_approx_units_built()) exact = true;   // (no approximate copy: of the two-sided kernels; in a default build)
     td = md == fast::MODE_GLA && (!semi || hopk) && !use_template && !keep_state && RR <= 16 && !two;
-    // (the reference-chain build leaves the real-FFT split unscaled, which is exact only for a power-of-two fwd_scale / 2)
-    if (exact && pl.cfg.normalized && !hopk) td = false;
+    // (the signal-form kernels leave the real-FFT split unscaled, which is exact only for a power-of-two fwd_scale / 2)
+    if (pl.cfg.normalized && !hopk) td = false;
     // k_hop_td writes two signals and re-reads z_t where k_hop writes one: at large hops its emission loop overtakes the saved state
     // traffic.  Measured crossovers (late iterations, 65 536 frames, tools/log/EXPERIMENTS.md r02 hop_td2), emission two samples at a time (even hop,
     // padding and length) / one at a time: n_fft 2048: wins up to hop 768 (0.350 vs 0.367 ms), loses at 1000 / wins at 333, loses at
@@ -400,7 +377,6 @@ struct FastState<float> {
       SI_TRY(mpairs2.reserve((size_t)nf * (G::H / 2) * 64 * sizeof(v4f)));
       SI_TRY(mmid2.reserve(nf * sizeof(float)));
     }
-    SI_TRY(inv_env.reserve(pl.length * sizeof(float)));
     cur = 0;
     SI_CHECK(!two || spec_user != nullptr, SPECINV_ESTATE, "the two-sided frame kernel takes its starting spectrum in the user layout");
     if (spec_user == nullptr) {
@@ -454,11 +430,6 @@ struct FastState<float> {
       SI_HIP(hipMemsetAsync(Umid.p, 0, nf * sizeof(v2f), pl.stream));
       xu_valid = true;
     }
-    if (hopk) {
-      hipLaunchKernelGGL(fast::k_reciprocal, dim3((unsigned)ceil_div(pl.length, 256)), dim3(256), 0, pl.stream,
-                         pl.env.template as<float>(), inv_env.template as<float>(), (long long)pl.length, exact ? 1 : 0);
-      SI_HIP(hipGetLastError());
-    }
     if (semi) {
       // x0 = ISTFT(start spectrum): synthesis frames from the pair layout, then the overlap-add
       if constexpr (RR <= 16) {
@@ -468,9 +439,6 @@ struct FastState<float> {
       SI_HIP(hipStreamSynchronize(pl.stream));   // *sum_m2_out is valid from here on
       return SPECINV_OK;
     }
-    hipLaunchKernelGGL(fast::k_reciprocal, dim3((unsigned)ceil_div(pl.length, 256)), dim3(256), 0, pl.stream,
-                       pl.env.template as<float>(), inv_env.template as<float>(), (long long)pl.length, exact ? 1 : 0);
-    SI_HIP(hipGetLastError());
     SI_HIP(hipMemsetAsync(xtail[0].p, 0, tail_bytes, pl.stream));   // x0 below is written whole
     // x0 = ISTFT(start spectrum) (methods.py:233 / :453) straight from the pair layout
     fast::FastArgs a{};
@@ -478,7 +446,7 @@ struct FastState<float> {
     a.P_in = Pb[0].template as<v4f>();
     a.Pmid_in = Pmid[0].template as<v2f>();
     a.window = pl.window.template as<float>();
-    a.inv_env = inv_env.template as<float>();
+    a.env = pl.env.template as<float>();
     a.T = pl.Tn();
     a.nchunks = nchunks;
     a.skew = skew;
@@ -493,7 +461,6 @@ struct FastState<float> {
     }
     if (OV == 4) fn = (const void*)fast::k_fused_istft<RR, 4>;
     if (OV == 2) fn = (const void*)fast::k_fused_istft<RR, 2>;
-    if (!exact && fn != nullptr) fn = approx_fused(RR, OV, 2, 0, 0);
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void* kargs[] = {&a};
@@ -642,7 +609,6 @@ struct FastState<float> {
       if (OV == 4) fn = (const void*)fast::k_fused<RR, 4, MODE, EVAL>;
     }
     if (OV == 2) fn = (const void*)fast::k_fused<RR, 2, MODE, EVAL>;
-    if (!exact && fn != nullptr) fn = approx_fused(RR, OV, MODE, EVAL ? 1 : 0, ((RR == 8 || RR == 16) && OV == 4 && !use_template) ? 1 : 0);
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
     const int wgw = fused_wgw();
     const size_t lds_used = G::lds_bytes(wgw);
@@ -675,7 +641,6 @@ struct FastState<float> {
                        else { if (OV == 4) fn = td_kernel<RR, 4>(early, ev); }
                        if (OV == 2) fn = td_kernel<RR, 2>(early, ev);
                      });
-    if (!exact && fn != nullptr) fn = specinv_approx_td(R, OV, early ? 1 : 0, ev ? 1 : 0, ((R == 8 || R == 16) && OV == 4) ? 1 : 0);
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
     fast::FastArgs args = a;
@@ -715,10 +680,7 @@ struct FastState<float> {
     s.hop = pl.cfg.hop_length;
     s.pad = pl.pad;
     const size_t lds = G::lds_bytes(4);
-    // (two-sided: the reference's operation order only - the approximate copy is not built for k_semi2)
-    const void* fn = two ? (const void*)fast::k_semi2<RR, MODE, EVAL>
-                         : !exact ? specinv_approx_frame(0, RR, MODE, EVAL ? 1 : 0) : (const void*)fast::k_semi<RR, MODE, EVAL>;
-    SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no approximate-projection frame kernel for this shape");
+    const void* fn = two ? (const void*)fast::k_semi2<RR, MODE, EVAL> : (const void*)fast::k_semi<RR, MODE, EVAL>;
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void* kargs[] = {&s};
     SI_HIP(hipLaunchKernel(fn, dim3(semi_grid), dim3(256), kargs, lds, pl.stream));
@@ -757,21 +719,19 @@ struct FastState<float> {
       a.m2_pairs = mpairs2.template as<v4f>();
       a.m2_mid = mmid2.template as<float>();
     }
-    s.env = inv_env.template as<float>();
+    s.env = pl.env.template as<float>();
     s.xtail = xtail[0].template as<float>();
     s.hop = hop;
     s.pad = pl.pad;
     const size_t lds = G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float);
-    const void* fn = two ? (const void*)fast::k_hop2<RR, MODE, EVAL>
-                         : !exact ? specinv_approx_frame(1, RR, MODE, EVAL ? 1 : 0) : (const void*)fast::k_hop<RR, MODE, EVAL>;
-    SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no approximate-projection chunked frame kernel for this shape");
+    const void* fn = two ? (const void*)fast::k_hop2<RR, MODE, EVAL> : (const void*)fast::k_hop<RR, MODE, EVAL>;
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void* kargs[] = {&s};
     SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
     if (nchunks > 1 && keep > 0) {
       const long long total = (long long)pl.B() * (nchunks - 1) * keep;
       hipLaunchKernelGGL(fast::k_hop_tails, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, pl.stream, a.x_out,
-                         (const float*)s.xtail, s.env, pl.Tn(), nchunks, hop, keep, pl.pad, (long long)pl.length, total, exact ? 1 : 0);
+                         (const float*)s.xtail, s.env, pl.Tn(), nchunks, hop, keep, pl.pad, (long long)pl.length, total);
       SI_HIP(hipGetLastError());
     }
     cur = nx;
@@ -809,7 +769,7 @@ struct FastState<float> {
     a.coef = pl.coef;
     a.fwd_scale = pl.fc.fwd_scale;
     a.inv_scale = pl.fc.inv_scale;
-    s.env = inv_env.template as<float>();
+    s.env = pl.env.template as<float>();
     s.xtail = xtail[0].template as<float>();
     s.hop = hop;
     s.pad = pl.pad;
@@ -817,8 +777,6 @@ struct FastState<float> {
     const size_t lds = G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float);
     const void* fn = early ? (ev ? (const void*)fast::k_hop_td<RR, true, true> : (const void*)fast::k_hop_td<RR, true, false>)
                            : (ev ? (const void*)fast::k_hop_td<RR, false, true> : (const void*)fast::k_hop_td<RR, false, false>);
-    if (!exact) fn = specinv_approx_frame(2, RR, early ? 1 : 0, ev ? 1 : 0);
-    SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no approximate-projection chunked frame kernel for this shape");
     SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     void* kargs[] = {&s};
     SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
@@ -826,7 +784,7 @@ struct FastState<float> {
       const long long total = (long long)pl.B() * (nchunks - 1) * keep;
       hipLaunchKernelGGL(fast::k_hop_tails_td, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, pl.stream, a.x2_out, a.x_out,
                          a.x_in, (const float*)s.xtail, s.env, a.coef, pl.Tn(), nchunks, hop, keep, pl.pad, (long long)pl.length,
-                         total, exact ? 1 : 0);
+                         total);
       SI_HIP(hipGetLastError());
     }
     cur = nx;
@@ -880,7 +838,7 @@ struct FastState<float> {
       a.m_pairs = mpairs.template as<v4f>();
       a.m_mid = mmid.template as<float>();
       a.window = pl.window.template as<float>();
-      a.inv_env = inv_env.template as<float>();
+      a.env = pl.env.template as<float>();
       a.partials = pl.partials.template as<double>();
       a.T = pl.Tn();
         a.nchunks = nchunks;

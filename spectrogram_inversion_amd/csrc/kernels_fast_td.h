@@ -5,7 +5,7 @@
 #include "fast_core.h"
 
 namespace specinv {
-namespace SI_FAST_NS {
+namespace fast {
 
 // ---- Griffin-Lim with the momentum carried in the time domain (every fused shape: hop = n_fft/2, /4, /8) ---------------------
 // methods.py:243-244 keep pre_t = STFT(x_t) - lr * pre_{t-1}, a (B, F, T) complex array read and written every iteration
@@ -137,13 +137,13 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   // every frame (the evaluating variant has no registers to spare and keeps loading)
   constexpr bool ENVREG = !EVAL;
   v2f envc[ENVREG ? QU : 1];
-  v2f envr[(ENVREG && SPECINV_IEEE) ? QU : 1];     // (reference chain: the envelope block and its correctly rounded reciprocal)
+  v2f envr[ENVREG ? QU : 1];     // (the envelope block and its correctly rounded reciprocal)
   if (ENVREG) {
-    const v2f* e0 = reinterpret_cast<const v2f*>(a.inv_env + (long long)(NB - PB) * HOP);
+    const v2f* e0 = reinterpret_cast<const v2f*>(a.env + (long long)(NB - PB) * HOP);
 #pragma unroll
     for (int i = 0; i < QU; ++i) {
       envc[i] = e0[64u * i + ulane];
-      if (SPECINV_IEEE) envr[SPECINV_IEEE ? i : 0] = env_rcp(envc[i]);
+      envr[i] = env_rcp(envc[i]);
     }
   }
   // the real-FFT twiddles of the pairs, W_N^(lane + 64 j): the plain launches have the registers to keep all of them (two waves
@@ -257,10 +257,13 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 
     // ---- per pair: split -> (+ c0 term) -> projection -> fold back
     v2f back[H];
-#if SPECINV_IEEE
     // The reference's operation order (ref_rcp_abs2, fast_core.h), written breadth-first over the frame's H pairs: every step of
     // the chain of dependent packed operations is issued for all pairs before the next one, so that no instruction waits on the
     // one just before it (the compiler pads such pairs with s_nop: 44 in the frame loop instead of 106).
+    // Nothing but the projection reads the bins, and it divides by their magnitude: the 1/2 fwd_scale of the split is left out
+    // (late launches) or moved onto the c0 term's factor (early launches: S / s = raw + (tds / s) c0, one packed multiply-add per
+    // bin).  This is exact, not approximate: the kernel is only taken for fwd_scale = 1, the factor 2 scales every intermediate
+    // result without a rounding, and the guard / floor constants are doubled / quadrupled with it.
     {
       v2f sk[H], sm[H], tt[H], yy[H], hh[H];
 #pragma unroll
@@ -304,47 +307,11 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
         back[j] = conj_sub_i(e2i, o2i);
       }
     }
-#else
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-      const v2f wk = WKREG ? wkr[WKREG ? j : 0] : pair_twiddle<R>(wn, j);
-      v2f sk, sm;
-      // nothing but the projection reads the bins, and it divides by their magnitude: the 1/2 fwd_scale of the split is left
-      // out (late launches) or moved onto the c0 term's factor (early launches: S / s = raw + (tds / s) c0, one packed
-      // multiply-add per bin).  With the reference's operation chain (SPECINV_IEEE) this is exact, not approximate: the
-      // kernel is only taken for fwd_scale = 1, the factor 2 scales every intermediate result without a rounding, and the
-      // guard / floor constants are doubled / quadrupled with it.
-      td_split_raw<R>(z[j], rc[R - 1 - j - H], wk, sk, sm);
-      if (EARLY) {
-        sk = __builtin_elementwise_fma(v2f{pp[j].x, pp[j].y}, v2f{tds_raw, tds_raw}, sk);
-        sm = __builtin_elementwise_fma(v2f{pp[j].z, pp[j].w}, v2f{tds_raw, tds_raw}, sm);
-      }
-      const float mk = (j & 1) ? mm[j / 2].z : mm[j / 2].x;
-      const float mq = (j & 1) ? mm[j / 2].w : mm[j / 2].y;
-      // the projection's factors (proj_rsq, fast_core.h) of the pair's two bins, formed and applied as packed operations
-      const v2f inv = v2f{proj_rsq(sk), proj_rsq(sm)};
-      const v2f mi = v2f{mk, mq} * inv;                       // (the inverse scale rides on the synthesis window)
-      v2f ak = scale_lo(sk, mi);
-      v2f am = scale_hi(sm, mi);
-      if (j == 0 && lane == 0) {   // bins 0 and M: irfft ignores their imaginary parts
-        ak.y = 0.0f;
-        am.y = 0.0f;
-      }
-      const v2f e2i = add_conj(ak, am);
-      const v2f o2i = cmulc(sub_conj(ak, am), wk);
-      z[j] = add_i(e2i, o2i);
-      back[j] = conj_sub_i(e2i, o2i);
-    }
-#endif
     v2f zmid;
     {
       v2f smid = z[H] * v2f{a.fwd_scale, -a.fwd_scale};
       if (EARLY) smid = v2f{fmaf(a.tds, pmid.x, smid.x), fmaf(a.tds, pmid.y, smid.y)};
-#if SPECINV_IEEE
       const v2f am = (smid * mmid) * ref_rcp_abs(ref_norm2(smid));
-#else
-      const v2f am = smid * (mmid * proj_rsq(smid));
-#endif
       zmid = am * v2f{2.0f, -2.0f};
     }
 #pragma unroll
@@ -361,7 +328,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_wins[64 * u + lane];
     if (t >= PB) {
       const long long o0 = (long long)(t - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);   // uniform
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);   // uniform
       v2f* xo = reinterpret_cast<v2f*>(xorow + o0);
       v2f* zo = reinterpret_cast<v2f*>(zorow + o0);
       // The envelope block: the register copy wherever it is valid.  The first frames of an item load theirs - in an arm of
@@ -379,7 +346,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 #pragma unroll
         for (int i = 0; i < QU; ++i) {
           ev[i] = envc[ENVREG ? i : 0];
-          er[i] = envr[(ENVREG && SPECINV_IEEE) ? i : 0];
+          er[i] = envr[ENVREG ? i : 0];
         }
       } else {
 #pragma unroll
@@ -410,7 +377,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 #pragma unroll
     for (int q = 0; q < PB - 1; ++q) {
       const long long o0 = (long long)(a.T + q - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
       v2f* xo = reinterpret_cast<v2f*>(xorow + o0);
       v2f* zo = reinterpret_cast<v2f*>(zorow + o0);
 #pragma unroll
@@ -425,7 +392,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     v2f* tl = reinterpret_cast<v2f*>(a.xtail_out + ((long long)b * a.nchunks + c) * NB * HOP);
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + (long long)(t_end + q - PB) * HOP);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + (long long)(t_end + q - PB) * HOP);
 #pragma unroll
       for (int i = 0; i < QU; ++i) tl[(q * QU + i) * 64u + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
     }
@@ -556,5 +523,5 @@ __global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a) {
   }
 }
 
-}  // namespace SI_FAST_NS (fast, or fast_approx in the approximate-projection units)
+}  // namespace fast
 }  // namespace specinv

@@ -7,7 +7,7 @@
 #include "fast_core.h"
 
 namespace specinv {
-namespace SI_FAST_NS {
+namespace fast {
 
 // ---- stand-alone transforms on the wave-level FFT (any hop; used by specinv_stft and the L_BFGS objective) ----
 
@@ -564,17 +564,11 @@ __device__ __forceinline__ void semi_frame_td(const FastArgs& a, long long fi, c
     }
     const float mk = (j & 1) ? mm[j / 2].z : mm[j / 2].x;
     const float mq = (j & 1) ? mm[j / 2].w : mm[j / 2].y;
-#if SPECINV_IEEE
     // (s m) r with r the correctly rounded 1 / |s|: the reference's operation order (ref_rcp_abs2, fast_core.h)
     const v2f rr = ref_rcp_abs2(v2f{ref_norm2(sk), ref_norm2(sm)});
     const v2f mp = v2f{mk, mq};
     v2f ak = scale_lo(scale_lo(sk, mp), rr) * a.inv_scale;
     v2f am = scale_hi(scale_hi(sm, mp), rr) * a.inv_scale;
-#else
-    const v2f mi = (v2f{mk, mq} * v2f{proj_rsq(sk), proj_rsq(sm)}) * a.inv_scale;
-    v2f ak = scale_lo(sk, mi);
-    v2f am = scale_hi(sm, mi);
-#endif
     if (j == 0 && lane == 0) {   // bins 0 and M: irfft ignores their imaginary parts
       ak.y = 0.0f;
       am.y = 0.0f;
@@ -588,11 +582,7 @@ __device__ __forceinline__ void semi_frame_td(const FastArgs& a, long long fi, c
   {
     v2f smid = z[H] * v2f{a.fwd_scale, -a.fwd_scale};
     if (EARLY) smid = v2f{fmaf(a.tds, pmid.x, smid.x), fmaf(a.tds, pmid.y, smid.y)};
-#if SPECINV_IEEE
     const v2f am = ((smid * mmid) * ref_rcp_abs(ref_norm2(smid))) * a.inv_scale;
-#else
-    const v2f am = smid * ((mmid * proj_rsq(smid)) * a.inv_scale);
-#endif
     zmid = am * v2f{2.0f, -2.0f};
   }
 #pragma unroll
@@ -855,5 +845,5 @@ __global__ __launch_bounds__(512, 1) void k_hop_inverse(HopInvArgs a) {
 
 
 
-}  // namespace SI_FAST_NS (fast, or fast_approx in the approximate-projection units)
+}  // namespace fast
 }  // namespace specinv

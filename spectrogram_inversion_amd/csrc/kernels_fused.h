@@ -4,7 +4,7 @@
 
 
 namespace specinv {
-namespace SI_FAST_NS {
+namespace fast {
 
 template <int R, int MODE, bool EVAL>
 __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves : kMinWaves) void k_fused4(FastArgs a) {
@@ -52,14 +52,15 @@ __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves
 #pragma unroll
   for (int i = 0; i < 3 * QU; ++i) acc[i] = v2f{0.0f, 0.0f};
   double sd = 0.0, so = 0.0;
-  // one block of the envelope reciprocal, periodic in the hop from hop-block 3 on (kernels_fast_td.h), kept in registers
+  // one block of the envelope and its correctly rounded reciprocal, periodic in the hop from hop-block 3 on (kernels_fast_td.h),
+  // kept in registers
   v2f envc[QU];
-  v2f envr[SPECINV_IEEE ? QU : 1];   // (reference chain: the envelope and its correctly rounded reciprocal)
-  const v2f* e0 = reinterpret_cast<const v2f*>(a.inv_env + (long long)HOP);
+  v2f envr[QU];
+  const v2f* e0 = reinterpret_cast<const v2f*>(a.env + (long long)HOP);
 #pragma unroll
   for (int i = 0; i < QU; ++i) {
     envc[i] = e0[64u * i + ulane];
-    if (SPECINV_IEEE) envr[SPECINV_IEEE ? i : 0] = env_rcp(envc[i]);
+    envr[i] = env_rcp(envc[i]);
   }
   TwRegs<R> twr;
 #pragma unroll
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
     if (live && t >= 2) {
       const long long o0 = (long long)(t - 2) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);   // uniform
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);   // uniform
       v2f* outp = reinterpret_cast<v2f*>(orow + o0);
       // (the envelope block: register copy, or - first frames of an item - loaded and waited for in an arm of its own; see
       // fused_td_body, kernels_fast_td.h)
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves
 #pragma unroll
         for (int i = 0; i < QU; ++i) {
           ev[i] = envc[i];
-          er[i] = envr[SPECINV_IEEE ? i : 0];
+          er[i] = envr[i];
         }
       } else {
 #pragma unroll
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves
   if (t_end == a.T) {
     // the chunk that holds the last frame also finishes hop-block T (frames T-3 .. T-1)
     const long long o0 = (long long)(a.T - 2) * HOP;
-    const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);
+    const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
     v2f* outp = reinterpret_cast<v2f*>(orow + o0);
 #pragma unroll
     for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[i], envp[64u * i + ulane]);
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(R == 8 ? 768 : 64 * kFused4Waves, R == 8 ? kR8Waves
     v2f* tl = reinterpret_cast<v2f*>(a.xtail_out + ((long long)b * a.nchunks + c) * 3 * HOP);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + (long long)(t_end + q - 2) * HOP);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + (long long)(t_end + q - 2) * HOP);
 #pragma unroll
       for (int i = 0; i < QU; ++i) tl[(q * QU + i) * 64u + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
     }
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : R == 8 ? kR8Waves : kMinWaves) v
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
     if (live && t >= PB) {
       const long long o0 = (long long)(t - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);   // uniform
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);   // uniform
       v2f* outp = reinterpret_cast<v2f*>(orow + o0);
 #pragma unroll
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[i] + z[i], envp[64u * i + ulane]);
@@ -443,7 +444,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : R == 8 ? kR8Waves : kMinWaves) v
 #pragma unroll
     for (int q = 0; q < PB - 1; ++q) {
       const long long o0 = (long long)(a.T + q - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
       v2f* outp = reinterpret_cast<v2f*>(orow + o0);
 #pragma unroll
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : R == 8 ? kR8Waves : kMinWaves) v
     v2f* tl = reinterpret_cast<v2f*>(a.xtail_out + ((long long)b * a.nchunks + c) * NB * HOP);
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + (long long)(t_end + q - PB) * HOP);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + (long long)(t_end + q - PB) * HOP);
 #pragma unroll
       for (int i = 0; i < QU; ++i) tl[(q * QU + i) * 64u + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
     }
@@ -541,7 +542,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
     if (live && t >= PB) {
       const long long o0 = (long long)(t - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
       v2f* outp = reinterpret_cast<v2f*>(orow + o0);
 #pragma unroll
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[i] + z[i], envp[64u * i + ulane]);
@@ -557,7 +558,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
 #pragma unroll
     for (int q = 0; q < PB - 1; ++q) {
       const long long o0 = (long long)(a.T + q - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.inv_env + o0);
+      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
       v2f* outp = reinterpret_cast<v2f*>(orow + o0);
 #pragma unroll
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
@@ -566,5 +567,5 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
 }
 
 
-}  // namespace SI_FAST_NS (fast, or fast_approx in the approximate-projection units)
+}  // namespace fast
 }  // namespace specinv

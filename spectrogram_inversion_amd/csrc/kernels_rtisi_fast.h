@@ -16,12 +16,6 @@
 #pragma once
 #include "rtisi_fast_args.h"
 
-#if SPECINV_IEEE
-#define RTISI_MSCALE a.inv_scale     // the target carries the inverse transform's scale (a power of two: exact)
-#else
-#define RTISI_MSCALE 1.0f
-#endif
-
 namespace specinv {
 namespace fast {
 
@@ -167,8 +161,8 @@ __global__ __launch_bounds__(MAXT, 1) void k_rtisi_fast(RtisiFastArgs a) {
     if (!kAhead) request_target(i);
     v4f mm[H / 2];
 #pragma unroll
-    for (int j = 0; j < H / 2; ++j) mm[j] = mnext[j] * RTISI_MSCALE;
-    float mmid = mnext_mid * RTISI_MSCALE;
+    for (int j = 0; j < H / 2; ++j) mm[j] = mnext[j] * a.inv_scale;   // (the inverse transform's scale: a power of two, exact)
+    float mmid = mnext_mid * a.inv_scale;
     if (kAhead) request_target(i + 1);
 
     // ---- overlap-add (methods.py:365-370), the part that does not change during the inner iterations: the kept
@@ -256,15 +250,10 @@ __global__ __launch_bounds__(MAXT, 1) void k_rtisi_fast(RtisiFastArgs a) {
         pre[j] = v4f{sk.x, sk.y, sm.x, sm.y};        // :392
         const float mk = (j & 1) ? mm[j / 2].z : mm[j / 2].x;
         const float mq = (j & 1) ? mm[j / 2].w : mm[j / 2].y;
-#if SPECINV_IEEE
         // :394-396 in the reference's operation order, (s m) r with r the correctly rounded 1 / |s| (fast_core.h: ref_rcp_abs, as in
         // the Griffin-Lim / ADMM kernels since round 4); the inverse transform's 1 / n_fft - a power of two - rides on m
         const v2f rr = ref_rcp_abs2(v2f{ref_norm2(sk), ref_norm2(sm)});
         const float ik = rr.x, im = rr.y;
-#else
-        const float ik = __builtin_amdgcn_rcpf(fast_abs(sk) + 1e-16f) * a.inv_scale;   // :394-396
-        const float im = __builtin_amdgcn_rcpf(fast_abs(sm) + 1e-16f) * a.inv_scale;
-#endif
         v2f ak = v2f{(sk.x * mk) * ik, (sk.y * mk) * ik};
         v2f am = v2f{(sm.x * mq) * im, (sm.y * mq) * im};
         if (j == 0 && lane == 0) {
@@ -282,11 +271,7 @@ __global__ __launch_bounds__(MAXT, 1) void k_rtisi_fast(RtisiFastArgs a) {
         const v2f p = premid;
         const v2f s = v2f{fmaf(-lr, p.x, xmid.x), fmaf(-lr, p.y, xmid.y)};
         premid = s;
-#if SPECINV_IEEE
         const float inv = ref_rcp_abs(ref_norm2(s));
-#else
-        const float inv = __builtin_amdgcn_rcpf(fast_abs(s) + 1e-16f) * a.inv_scale;
-#endif
         zmid = v2f{(s.x * mmid) * inv, (s.y * mmid) * inv} * v2f{2.0f, -2.0f};
       }
 #pragma unroll

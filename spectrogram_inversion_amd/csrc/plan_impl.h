@@ -635,7 +635,6 @@ struct PlanT final : PlanBase {
     const C* start_user = static_cast<const C*>(init_spec);
     keep_latched = keep_state;
     fast.keep_state = keep_state;
-    fast.exact = exact;
     if constexpr (std::is_same<T, float>::value) {
       // fused kernels, magnitude input: phase_init writes the pair layout itself (methods.py:106 without the (B, F, T)
       // complex round trip and the two layout passes)

@@ -147,7 +147,7 @@ extern "C" {
 
 const char* specinv_last_error(void) { return last_error().c_str(); }
 int specinv_abi_version(void) { return SPECINV_ABI_VERSION; }
-int specinv_has_approx(void) { return specinv_approx_units_built(); }
+int specinv_has_approx(void) { return 0; }   // (kept for compatibility: there are no approximate-projection kernels)
 
 int specinv_plan_create(const specinv_stft_cfg* cfg, specinv_plan** out) {
   SI_CHECK(cfg && out, SPECINV_EINVAL, "null argument");
@@ -198,14 +198,13 @@ int specinv_plan_launch_geometry(const specinv_plan* plan, int32_t out[4]) {
 int specinv_plan_keep_state(specinv_plan* plan, int on) {
   PLAN_OR_FAIL(plan);
   // one-sided plans re-read the flag on every iterate(); a two-sided float32 plan picks its KERNELS by it (the frame kernel carries
-  // Y = X + U alone, keep_state takes the coverage kernels and their buffers, reserved by *_init) and latches it there: like
-  // specinv_plan_set_exact it is read by the next specinv_gla_init / specinv_admm_init, a running method keeps its kernels
+  // Y = X + U alone, keep_state takes the coverage kernels and their buffers, reserved by *_init) and latches it there: it is read
+  // by the next specinv_gla_init / specinv_admm_init, a running method keeps its kernels
   plan->impl->keep_state = on != 0;
   return SPECINV_OK;
 }
-int specinv_plan_set_exact(specinv_plan* plan, int on) {
-  PLAN_OR_FAIL(plan);
-  plan->impl->exact = on != 0;          // (read by the next specinv_gla_init / specinv_admm_init: a running method keeps its kernels)
+int specinv_plan_set_exact(specinv_plan* plan, int) {
+  PLAN_OR_FAIL(plan);                   // (kept for compatibility: the reference's operation order is the only arithmetic)
   return SPECINV_OK;
 }
 int specinv_plan_force_generic(specinv_plan* plan, int on) {

@@ -95,14 +95,13 @@ def _iterative_sliced(which, spec3, args, device, rdtype, coef, max_iter, tol, v
     stop rule of `_training_loop` (torch_specinv/methods.py:181-190) are whole-batch quantities, so every evaluation adds the
     slices' sums before the decision - what `distributed.run_loop_global` does across ranks, here across slices."""
     from .metrics import _from_sums
-    from .plan import Plan, exact_projection
+    from .plan import Plan
     assert eva_iter > 0 and max_iter > 0 and tol >= 0
     assert isinstance(metric, str) and metric.upper() in _lib.METRICS
     name = metric.upper()
     plans = []
     for lo, hi in _slices(spec3.shape[0]):
         p = Plan(args, hi - lo, spec3.shape[2], rdtype, device)
-        p.set_exact(exact_projection())
         part = spec3[lo:hi]
         init = getattr(p, which + "_init")
         if part.is_complex():

@@ -186,11 +186,9 @@ class Plan:
         _lib.check(self.lib.specinv_plan_force_generic(self._h, int(on)))
 
     def set_exact(self, on=True):
-        """The arithmetic of the magnitude projection and of the envelope division on the float32 wave-level kernels
-        (torch_specinv/methods.py:132,246-247).  True (the library's default): the reference's operation order, (S m) r with r the
-        correctly rounded 1 / |S|, and a correctly rounded division by the envelope; False: the approximate copies of the kernels
-        (S (m rsq(|S|^2)), multiplication by 1 / envelope; 3 % faster on the headline step).  Call before `gla_init` /
-        `admm_init`: the next init picks the kernels (a running method keeps its own)."""
+        """Kept for compatibility; does nothing.  The float32 wave-level kernels always use the reference's operation order in
+        the magnitude projection and the envelope division (torch_specinv/methods.py:132,246-247): (S m) r with r the correctly
+        rounded 1 / |S|, and a correctly rounded division by the envelope."""
         _lib.check(self.lib.specinv_plan_set_exact(self._h, int(on)))
 
     def keep_state(self, on=True):
@@ -637,33 +635,18 @@ def get_plan(args: StftArgs, batch: int, n_frames: int, dtype: torch.dtype, devi
     else:
         cache.move_to_end(key)
         plan.keep_state(False)                 # (a per-run request: the next user of a cached plan gets the default kernels)
-    plan.set_exact(exact_projection())
     trim_plan_cache()
     return plan
 
 
-_EXACT = [None]
-
-
 def set_exact_projection(on: bool | None):
-    """Module-level switch for the drop-in functions (their signatures are the reference's, so the choice cannot be an
-    argument): True = the reference's operation order in the projection and a true envelope division on every plan the public
-    functions create from now on (the default), False = the approximate kernels (3 % faster on the headline step),
-    None = follow the environment (SPECINV_EXACT=0 selects the approximations)."""
-    _EXACT[0] = on
+    """Kept for compatibility; does nothing: the drop-in functions always use the reference's operation order in the
+    projection and a true envelope division (`Plan.set_exact`)."""
 
 
 def has_approx() -> bool:
-    """Does the loaded library carry the approximate-projection kernels (built with SPECINV_BUILD_APPROX=1)?  Without them
-    `set_exact(False)` / `set_exact_projection(False)` / SPECINV_EXACT=0 are accepted and every plan keeps the reference's operation
-    order."""
-    return bool(_lib.load().specinv_has_approx())
-
-
-def exact_projection() -> bool:
-    if _EXACT[0] is not None:
-        return bool(_EXACT[0])
-    return os.environ.get("SPECINV_EXACT", "1") != "0"
+    """Kept for compatibility: the library carries no approximate-projection kernels, so this is always False."""
+    return False
 
 
 def trim_plan_cache():

@@ -48,10 +48,9 @@ def kernels():
     return t
 
 
-def _find(table, *parts, approx=False):
-    """the kernel whose mangled name holds every part, in namespace fast (default: the reference's operation order in the projection)
-    or fast_approx (the copy with the approximate projection)"""
-    hits = [k for k in table if all(p in k for p in parts) and ("11fast_approx" in k) == approx]
+def _find(table, *parts):
+    """the kernel whose mangled name holds every part"""
+    hits = [k for k in table if all(p in k for p in parts)]
     assert len(hits) == 1, (parts, hits)
     return table[hits[0]]
 
@@ -68,10 +67,6 @@ def test_headline_kernels_keep_their_register_budgets(kernels):
     # C3: k_rtisi_fast<16, 256, 4> - one wave per SIMD, the whole 512-entry file, no spills
     v, sp, a = _find(kernels, "12k_rtisi_fastILi16ELi256ELi4E")
     assert v > 256 and sp == 0, (v, sp, a)
-    # the approximate-projection copy of the headline kernel (SPECINV_BUILD_APPROX=1 builds only) keeps the two-waves budget as well
-    if any("11fast_approx" in k for k in kernels):
-        v, sp, _ = _find(kernels, "11k_fused4_tdILi16ELb0ELb0E", approx=True)
-        assert v <= 256 and sp == 0, (v, sp)
     # C5: k_objective_logmel<16, 9, false, true> (the mel filterbank as bands) and <16, 5> (the same on the matrix cores) - two
     # waves per SIMD (<= 256 registers), no spills
     for name in ("18k_objective_logmelILi16ELi9ELb0ELb1E", "18k_objective_logmelILi16ELi5ELb0ELb0E"):
@@ -83,7 +78,7 @@ def test_no_shipped_wave_level_kernel_spills_heavily(kernels):
     """k_objective_logmel<8, 8> compiled to 256 registers + 978 spilled and ran 1.8 x slower than its neighbours <8, 7> / <8, 9> for
     a whole round before anybody looked: no kernel of the wave-level family may spill more than a hundred registers (the known
     heavy ones: the early evaluating launch, k_rtisi_fast with 512-sample hops at look-ahead 8)."""
-    bad = {k: v for k, v in kernels.items() if ("4fast" in k or "11fast_approx" in k) and v[1] > 140}
+    bad = {k: v for k, v in kernels.items() if "4fast" in k and v[1] > 140}
     assert not bad, bad
 
 

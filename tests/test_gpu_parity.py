@@ -95,7 +95,7 @@ def test_phase_init(i):
 # happen to fall on the same side).  Which side a kernel lands on is decided by 1e-7 of rounding in its FFT, not by the
 # projection's arithmetic: rounds 2 / 3 / 4 measured the event on the fused kernels with the approximate projection, on the frame
 # kernel with IEEE divisions and with one-rounding reciprocals, on the pre_spec kernel with two-rounding reciprocals
-# (tools/refchain_study.py, profiles/r04_refchain.txt); every other of the 45 strict-gate cases passes on every arithmetic.  The
+# (profiles/r04_refchain.txt); every other of the 45 strict-gate cases passes on every arithmetic.  The
 # cases listed here keep the segment-distribution form of the gate.
 STRICT_XFAIL = {(0.3, 100, "frame")}
 
@@ -133,20 +133,17 @@ def test_gla_waveforms(alpha, it):
         assert abs(sc_y - sc_ref) < 1e-5, (sc_y, sc_ref)
 
 
-@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("exact", [True])
 @pytest.mark.parametrize("path", ["frame", "fused", "fused_prespec"])
 @pytest.mark.parametrize("alpha", [0.0, 0.3, 0.99])
 @pytest.mark.parametrize("it", [10, 100])
 def test_gla_waveforms_every_kernel_and_arithmetic(alpha, it, path, exact, monkeypatch):
     """The g2 waveforms after 10 and 100 iterations on each float32 wave-level kernel - the frame kernel (default for a problem this
-    small), the signal-form fused kernel, the fused kernel on pre_spec - with the default arithmetic (`set_exact(True)`: the
-    reference's operation order, (S m) r with r the correctly rounded 1 / |S|, torch_specinv/methods.py:246-247; a true division by
-    the envelope, :132) and with the approximate copies (`set_exact(False)`).  Exact arithmetic: the STRICT gate
-    min(1e-4, 6 x the reference's float32-vs-float64 noise), the one near-zero event excepted (STRICT_XFAIL).  Approximate
-    arithmetic: the strict gate at 10 iterations, the segment-distribution form at 100."""
+    small), the signal-form fused kernel, the fused kernel on pre_spec - with the library's one arithmetic (`set_exact(True)`: the
+    reference's operation order, (S m) r with r the correctly rounded 1 / |S|, torch_specinv/methods.py:246-247; a true division
+    by the envelope, :132): the STRICT gate min(1e-4, 6 x the reference's float32-vs-float64 noise), the one near-zero event
+    excepted (STRICT_XFAIL).  (The approximate copies that `exact=False` once selected are retired.)"""
     from spectrogram_inversion_amd.plan import Plan
-    if not exact and not si.has_approx():
-        pytest.skip("the approximate-projection kernels are not in this build (SPECINV_BUILD_APPROX=1)")
     g = load_golden("g2_gla")
     hop, w = int(g["hop"]), torch.from_numpy(g["window"])
     key = f"a{alpha}_it{it}"
@@ -164,53 +161,53 @@ def test_gla_waveforms_every_kernel_and_arithmetic(alpha, it, path, exact, monke
     assert p.launch_geometry["kernel"] == want, p.launch_geometry
     p.run(it, 10, 0.0, "sc")
     y = N(p.wave())
-    err = rel_l2(y, ref)
-    if exact or it < 100:
-        _strict_or_segments(y, ref, gate, hop, (alpha, it, path), err)
-    else:
-        seg = segment_errors(y, ref, hop)
-        assert np.quantile(seg, 0.75) < gate and seg.max() < 3e-2, (alpha, path, err, np.quantile(seg, 0.75), seg.max())
+    _strict_or_segments(y, ref, gate, hop, (alpha, it, path), rel_l2(y, ref))
 
 
 def test_exact_projection_switch_of_the_drop_in_functions(monkeypatch):
-    """The module-level switch (the drop-in signatures are the reference's): the default is the reference's operation order;
-    `set_exact_projection(False)` / SPECINV_EXACT=0 make `griffin_lim` / `ADMM` take the approximate kernels - the result equals a
-    plan run with `set_exact(False)` and differs from the default arithmetic's in the last bits only."""
-    from spectrogram_inversion_amd.plan import Plan, clear_plan_cache
+    """The switches of the retired approximate-projection kernels are kept for compatibility and change nothing: `has_approx()` is
+    False, and `set_exact_projection(False)`, SPECINV_EXACT=0 and `Plan.set_exact(False)` each leave `griffin_lim` and `ADMM`
+    bit-identical to the default run, which is the reference's operation order."""
+    from spectrogram_inversion_amd.plan import Plan
     g = load_golden("g2_gla")
     kw = dict(hop_length=int(g["hop"]), window=torch.from_numpy(g["window"]))
     init = T(g["init"])
     monkeypatch.delenv("SPECINV_EXACT", raising=False)
-    if not si.has_approx():
-        # a default build (round 6) does not carry the approximate copies: the switch is accepted and changes nothing
-        want = N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw))
-        try:
-            si.set_exact_projection(False)
-            assert np.array_equal(N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw)), want)
-        finally:
-            si.set_exact_projection(None)
-        return
-    exact = N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw))
-    exact_admm = N(si.ADMM(init, max_iter=3, rho=1.0, tol=0, verbose=False, **kw))
+    assert si.has_approx() is False
+
+    def drop_in():
+        return (N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw)),
+                N(si.ADMM(init, max_iter=3, rho=1.0, tol=0, verbose=False, **kw)))
+
+    def planned(on):
+        out = []
+        for init_method, coef, n_iter in (("gla_init", 0.3, 10), ("admm_init", 1.0, 3)):
+            p = Plan(args_helper(init, **kw), init.shape[0], init.shape[2], torch.float32, dev())
+            if on is not None:
+                p.set_exact(on)
+            getattr(p, init_method)(init, None, coef)
+            p.iterate(n_iter)
+            out.append(N(p.wave()))
+        return out
+
+    gla, admm = drop_in()
     try:
         si.set_exact_projection(False)
-        approx = N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw))
-        approx_admm = N(si.ADMM(init, max_iter=3, rho=1.0, tol=0, verbose=False, **kw))
+        gla_off, admm_off = drop_in()
     finally:
         si.set_exact_projection(None)
+    assert np.array_equal(gla_off, gla) and np.array_equal(admm_off, admm)
     monkeypatch.setenv("SPECINV_EXACT", "0")
-    assert np.array_equal(N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw)), approx)
+    gla_env, admm_env = drop_in()
     monkeypatch.delenv("SPECINV_EXACT")
-    assert np.array_equal(N(si.griffin_lim(init, max_iter=10, alpha=0.3, tol=0, verbose=False, **kw)), exact)
-    for on, want in ((True, exact), (False, approx)):
-        p = Plan(args_helper(init, **kw), init.shape[0], init.shape[2], torch.float32, dev())
-        p.set_exact(on)
-        p.gla_init(init, None, 0.3)
-        p.iterate(10)
-        assert np.array_equal(N(p.wave()), want)
-    assert not np.array_equal(exact, approx) and rel_l2(exact, approx) < 1e-5
+    assert np.array_equal(gla_env, gla) and np.array_equal(admm_env, admm)
+    gla_plan, admm_plan = planned(None)
+    assert np.array_equal(gla_plan, gla)
+    for on in (True, False):
+        gla_on, admm_on = planned(on)
+        assert np.array_equal(gla_on, gla_plan) and np.array_equal(admm_on, admm_plan), on
     ref = oracle.admm(g["init"], max_iter=3, rho=1.0, tol=0, hop_length=int(g["hop"]), window=g["window"])
-    assert rel_l2(exact_admm, ref) < 1e-5 and rel_l2(approx_admm, ref) < 1e-5
+    assert rel_l2(admm, ref) < 1e-5
 
 
 @pytest.mark.parametrize("path", ["default", "fused", "fused_prespec", "frame_lds", "frame_lds_prespec", "generic", "generic_workgroup", "float64",

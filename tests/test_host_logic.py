@@ -298,22 +298,14 @@ def test_mel_filterbank_options():
     assert lim[:, hz < 290].sum() == 0 and lim[:, hz > 4010].sum() == 0
 
 
-def test_exact_projection_switch_and_progress_mode(monkeypatch):
-    """The module-level switches of round 3 (no GPU involved): `set_exact_projection` overrides SPECINV_EXACT, None follows it;
-    RTISI_LA's live progress bar is only taken when somebody can watch it (a terminal) or on request."""
+def test_compat_switches_and_progress_mode(monkeypatch):
+    """The module-level switches (no GPU involved): `has_approx` and `set_exact_projection` are kept for compatibility - there
+    are no approximate-projection kernels, and the switch accepts True / False / None (test_gpu_parity.py shows that it changes
+    nothing); RTISI_LA's live progress bar is only taken when somebody can watch it (a terminal) or on request."""
     from spectrogram_inversion_amd import plan as P, methods as M
-    monkeypatch.delenv("SPECINV_EXACT", raising=False)
-    P.set_exact_projection(None)
-    assert P.exact_projection() is True                     # (round 4: the reference's operation order is the default)
-    monkeypatch.setenv("SPECINV_EXACT", "0")
-    assert P.exact_projection() is False
-    P.set_exact_projection(True)
-    assert P.exact_projection() is True
-    P.set_exact_projection(False)
-    monkeypatch.setenv("SPECINV_EXACT", "1")
-    assert P.exact_projection() is False
-    P.set_exact_projection(None)
-    assert P.exact_projection() is True
+    assert P.has_approx() is False
+    for on in (True, False, None):
+        P.set_exact_projection(on)
     monkeypatch.setenv("SPECINV_RTISI_PROGRESS", "blocks")
     assert M._live_progress() is True
     monkeypatch.setenv("SPECINV_RTISI_PROGRESS", "end")
