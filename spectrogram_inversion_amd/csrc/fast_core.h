@@ -51,6 +51,8 @@ constexpr int kFused4Waves = 8;    // most waves per workgroup of k_fused4 / k_f
                                    // faster than 4-wave ones once every wave slot is filled
 constexpr int kR8Waves = 3;        // ... at n_fft 1024 (R = 8): three waves per SIMD, 12-wave workgroups (168 registers; against two:
                                    // C4 34.3 -> 32.3 ms per step, Griffin-Lim 1024 / 256 0.135 -> 0.127 ms per iteration)
+constexpr double kTdsFloor = 9.3132257461547852e-10;   // 2^-30: once |(-lr)^t| (FastArgs::tds) is below it the c0 term of the signal-form
+                                                       // kernels is under float32 resolution of |pre| and their EARLY = false variants run
 
 using v2f = float __attribute__((ext_vector_type(2)));
 using v4f = float __attribute__((ext_vector_type(4)));

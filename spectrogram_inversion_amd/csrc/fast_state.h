@@ -1,42 +1,13 @@
 // Host side of the wave-level kernels: FastState<float> picks the kernel, sizes the launch and owns the device state.
 #pragma once
 #include <algorithm>
+#include "dev_buf.h"
 #include "fast_core.h"
 #include "kernels_layout.h"
 
 namespace specinv {
 
 // ---- host side ---------------------------------------------------------------------------------------
-struct FastBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~FastBuf() {
-    if (p) {
-      (void)hipFree(p);
-      account_bytes(-(int64_t)bytes);
-    }
-  }
-  int reserve(size_t n) {
-    if (p && n <= bytes) return SPECINV_OK;
-    if (p) {
-      (void)hipFree(p);
-      account_bytes(-(int64_t)bytes);
-    }
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipMalloc(&p, n ? n : 16);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return fail(SPECINV_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(e));
-    }
-    bytes = n;
-    account_bytes((int64_t)n);
-    return SPECINV_OK;
-  }
-  template <typename U>
-  U* as() const { return static_cast<U*>(p); }
-};
-
 template <typename T>
 struct FastState {
   bool supported = false;
@@ -74,6 +45,98 @@ struct FastState {
     default: { constexpr int RR = 32; __VA_ARGS__; } break; \
   }
 
+// the address of K<..., EARLY, EVAL> (a signal-form kernel; `...`: its leading template arguments) for run-time `early` / `ev`
+#define SPECINV_EARLY_EVAL(early, ev, K, ...)                                                                     \
+  ((early) ? ((ev) ? (const void*)K<__VA_ARGS__, true, true> : (const void*)K<__VA_ARGS__, true, false>)          \
+           : ((ev) ? (const void*)K<__VA_ARGS__, false, true> : (const void*)K<__VA_ARGS__, false, false>))
+
+// The environment knobs of this file, read once when a plan is set up (FastState::setup): what a plan does afterwards does not
+// depend on when the environment was last changed.
+struct FastKnobs {
+  bool disable_fast = false;       // SPECINV_DISABLE_FAST=1: none of the kernels of this file
+  bool disable_twosided = false;   // SPECINV_DISABLE_TWOSIDED=1: two-sided spectrograms on the coverage kernels
+  bool disable_fused = false;      // SPECINV_DISABLE_FUSED=1 (tests): put the shape on the frame kernel
+  bool disable_hop = false;        // SPECINV_DISABLE_HOP=1: no overlap-add on the chip (k_semi + k_ola, inverse frames + gather)
+  bool fused_template = false;     // SPECINV_FUSED_TEMPLATE=1 (tests): k_fused<R, 4> where the tuned copy k_fused4<R> would run
+  bool eval_kernel = true;         // SPECINV_EVAL_KERNEL=0: the fused evaluating variant where k_eval_td would run
+  bool debug = false;              // SPECINV_DEBUG: the chosen launch on stderr
+  bool has_small_frames = false;   // SPECINV_SMALL_FRAMES=n: the frame count from which the chunk-walking kernels run (frames_from;
+  long long small_frames = 0;      //   tests pin them with 0)
+  int fast_chunk = 0;              // SPECINV_FAST_CHUNK=n: frames per chunk (experiments; 0: the planner's choice)
+  int cu_budget = 0;               // SPECINV_CU_BUDGET=k: plan for a chip of 256 - k compute units (setup)
+  bool has_k4_skew = false;        // SPECINV_K4_SKEW="s1,s2" (experiments; "0,0" switches the chunk triples off)
+  int k4_s1 = 0, k4_s2 = 0;
+  bool has_td_skew = false;        // SPECINV_TD_SKEW=n (experiments; 0 switches the skewed chunk pairs off)
+  int td_skew = 0;
+
+  static FastKnobs read() {
+    auto starts = [](const char* name, char c) {
+      const char* e = getenv(name);
+      return e != nullptr && e[0] == c;
+    };
+    FastKnobs k;
+    k.disable_fast = starts("SPECINV_DISABLE_FAST", '1');
+    k.disable_twosided = starts("SPECINV_DISABLE_TWOSIDED", '1');
+    k.disable_fused = starts("SPECINV_DISABLE_FUSED", '1');
+    k.disable_hop = starts("SPECINV_DISABLE_HOP", '1');
+    k.fused_template = starts("SPECINV_FUSED_TEMPLATE", '1');
+    k.eval_kernel = !starts("SPECINV_EVAL_KERNEL", '0');
+    k.debug = getenv("SPECINV_DEBUG") != nullptr;
+    if (const char* e = getenv("SPECINV_SMALL_FRAMES")) {
+      k.has_small_frames = true;
+      k.small_frames = atoll(e);
+    }
+    if (const char* e = getenv("SPECINV_FAST_CHUNK")) k.fast_chunk = atoi(e);
+    if (const char* e = getenv("SPECINV_CU_BUDGET")) k.cu_budget = atoi(e);
+    if (const char* e = getenv("SPECINV_K4_SKEW")) k.has_k4_skew = sscanf(e, "%d,%d", &k.k4_s1, &k.k4_s2) == 2;
+    if (const char* e = getenv("SPECINV_TD_SKEW")) {
+      k.has_td_skew = true;
+      k.td_skew = atoi(e);
+    }
+    return k;
+  }
+  // a frame-count threshold: the measured crossover unless SPECINV_SMALL_FRAMES overrides it
+  long long frames_from(long long measured) const { return has_small_frames ? small_frames : measured; }
+};
+
+// Frames per wave.  A launch takes about rounds x (longest chunk) frame times, rounds = ceil(waves / wave slots), e.g. 64 x 1024
+// frames on 2048 slots -> 32 chunks of 32 (2048 waves, one round), 96 x 1024 -> 21 chunks of 49 (2016 waves, one round) instead of
+// 32 chunks (3072 waves, two rounds).
+// (+2: what a chunk boundary costs - split blocks, pipeline fill; measured: 2 rounds of 16-frame chunks are 8 % slower than 1 round
+// of 32.  Last factor: chunks beyond 32 frames measured ~5 % slower than two rounds of 32)
+inline double chunk_cost(int batch, int n_frames, int nch, long long slots) {
+  const long long waves = (long long)batch * nch;
+  const long long rounds = (waves + slots - 1) / slots;
+  const int longest = (n_frames + nch - 1) / nch;
+  return (double)rounds * (longest + 2.0) * (1.0 + 0.0015 * std::max(0, longest - 32));
+}
+struct ChunkPick {
+  int nch = 0;
+  double cost = 1e300;
+};
+// the cheapest count of chunks per item among the multiples of `mult` in [lo, hi] (nch = 0: there is none); of costs within `tie`
+// of each other the larger count wins
+inline ChunkPick pick_chunks(int batch, int n_frames, long long slots, int lo, int hi, int mult = 1, double tie = 1e-9) {
+  ChunkPick best;
+  for (int nch = lo; nch <= hi; ++nch) {
+    if (nch % mult != 0) continue;
+    const double cost = chunk_cost(batch, n_frames, nch, slots);
+    if (cost < best.cost + tie) best = ChunkPick{nch, cost};
+  }
+  return best;
+}
+
+// the kernel FastState<float>::geometry reports (specinv_plan_launch_geometry, out[3]; plan.py's table of names goes by these values)
+enum FastKernel {
+  kKernelFused4 = 1,     // k_fused4
+  kKernelFused = 2,      // k_fused<R, OV>
+  kKernelSemi = 3,       // k_semi
+  kKernelHop = 4,        // k_hop
+  kKernelFused4Td = 5,   // k_fused4_td (hop = n_fft / 4 at n_fft 1024 / 2048)
+  kKernelFusedTd = 6,    // k_fused_td<R, OV> otherwise
+  kKernelHopTd = 7,      // k_hop_td
+};
+
 template <>
 struct FastState<float> {
   using v2f = fast::v2f;
@@ -84,25 +147,26 @@ struct FastState<float> {
   int semi_grid = 0;
   int R = 0;
   int OV = 0;          // n_fft / hop of the fused kernel (2, 4 or 8)
-  bool state_in_place = true;
-  bool use_template = false;   // tests: run k_fused<R, 4> where the tuned copy k_fused4<R> would run (SPECINV_FUSED_TEMPLATE=1)
+  FastKnobs knobs;
   int chunk = 32, nchunks = 0, n_waves = 0, n_partials = 0;
   int skew = 0;        // frames every odd chunk cedes to the even chunk before it (chunk_begin; set per Griffin-Lim run in begin_t)
-  int cur = 0;   // index of the buffers holding the current state
+  int cur = 0;   // index of the signal buffers (xb, xtail, zb) holding the current state
   int mode = fast::MODE_GLA;
-  FastBuf xb[2], xtail[2], Pb[2], Pmid[2], mpairs, mmid, scratch;
+  // x (and the chunk tails) ping-pong between iterations; the spectral state of a frame is read and written by the same lane, so it
+  // lives in one buffer (Pb, Pmid: same speed as ping-pong buffers, measured; a third less memory)
+  DevBuf xb[2], xtail[2], Pb, Pmid, mpairs, mmid, scratch;
   // a two-sided spectrogram (onesided=False): the frame kernel k_semi2 with the mirror bins' state and target beside the lower
   // half's (FastArgs::P2_out); no fused / chunked / signal-form kernels, no stand-alone transforms
   bool two = false;
-  FastBuf Pb2, Pmid2, mpairs2, mmid2;
+  DevBuf Pb2, Pmid2, mpairs2, mmid2;
   // ADMM carries Y = X + U in Pb (FastArgs).  X and U themselves are only written when the caller has asked for them
   // (specinv_plan_keep_state), by the last iteration of every iterate() call.
   bool keep_state = false, xu_valid = false;
-  FastBuf Xb, Xmid, Ub, Umid;
+  DevBuf Xb, Xmid, Ub, Umid;
   // Griffin-Lim on k_fused4_td: the momentum state is the signal z (zb), Pb keeps the starting spectrum c0
   bool td = false;
   int td_t = 0;          // closure calls so far (z_1 = x_1: the first call reads x itself)
-  FastBuf zb[2];
+  DevBuf zb[2];
 
   // the optional X / U outputs of an ADMM iteration (`last`: the last iteration of an iterate() call)
   template <typename P>
@@ -134,17 +198,14 @@ struct FastState<float> {
     xform_ok = false;
     two = false;
     if (cfg.dtype != SPECINV_F32) return SPECINV_OK;
-    if (const char* e = getenv("SPECINV_DISABLE_FAST")) {
-      if (e[0] == '1') return SPECINV_OK;
-    }
+    knobs = FastKnobs::read();
+    if (knobs.disable_fast) return SPECINV_OK;
     const bool size_ok = cfg.n_fft == 512 || cfg.n_fft == 1024 || cfg.n_fft == 2048 || cfg.n_fft == 4096;
     if (!size_ok) return SPECINV_OK;
     if (!cfg.onesided) {
       // two-sided: the frame kernels only - k_semi2 + gather overlap-add, or k_hop2 over chunks of frames (round 5;
       // SPECINV_DISABLE_TWOSIDED=1: the coverage kernels); no fused / signal-form kernels, no stand-alone transforms
-      if (const char* e = getenv("SPECINV_DISABLE_TWOSIDED")) {
-        if (e[0] == '1') return SPECINV_OK;
-      }
+      if (knobs.disable_twosided) return SPECINV_OK;
       if (pad >= length) return SPECINV_OK;
       two = true;
     } else {
@@ -153,23 +214,16 @@ struct FastState<float> {
     }
     R = cfg.n_fft / 128;
     semi = false;
-    state_in_place = true;     // (same speed as ping-pong buffers, measured; a third less memory)
-    use_template = false;
-    if (const char* e = getenv("SPECINV_FUSED_TEMPLATE")) use_template = e[0] == '1';
     // fused kernel: hop = n_fft / 2, / 4 or / 8 (whole registers per hop-block), centred, enough frames
     OV = 0;
     for (int o : {2, 4, 8})
       if (cfg.hop_length * o == cfg.n_fft && R % o == 0) OV = o;
-    if (two) OV = 0;
-    if (const char* e = getenv("SPECINV_DISABLE_FUSED")) {   // tests: put the shape on the frame kernel
-      if (e[0] == '1') OV = 0;
-    }
+    if (two || knobs.disable_fused) OV = 0;
+    const long long n_all = (long long)cfg.batch * cfg.n_frames;
     // small problems are latency-bound on the fused kernel (a wave walks >= 8 frames one after the other): below
     // ~6 k frames the frame kernel, one frame per wave, finishes an iteration sooner (measured: 1 x 512 frames at
     // n_fft 1024 10 vs 27 us, 16 x 256 26 vs 32 us; 16 x 512 at n_fft 2048 69 vs 55 us)
-    long long small_below = 6144;
-    if (const char* e = getenv("SPECINV_SMALL_FRAMES")) small_below = atoll(e);       // (tests pin the chunked kernel with 0)
-    const bool small = (long long)cfg.batch * cfg.n_frames < small_below;
+    const bool small = n_all < knobs.frames_from(6144);
     if (!cfg.center || OV == 0 || cfg.n_frames < OV + 2 || pad >= length || small) {
       // any other hop / centring: frame kernel on the wave-level FFT + gather overlap-add (k_semi)
       semi = true;
@@ -177,8 +231,7 @@ struct FastState<float> {
       OV = 0;
       chunk = cfg.n_frames;
       nchunks = 1;
-      const long long nf = (long long)cfg.batch * cfg.n_frames;
-      semi_grid = (int)std::min<long long>((nf + 3) / 4, 256 * 8);
+      semi_grid = (int)std::min<long long>((n_all + 3) / 4, 256 * 8);
       n_waves = semi_grid * 4;
       supported = true;
       // Large enough problems keep the overlap-add on the chip (k_hop): a wave per chunk of frames, 8-wave workgroups,
@@ -188,46 +241,24 @@ struct FastState<float> {
       // at n_fft 2048 and ~32 k frames at 1024 and 512)
       // (round 5's sweep, n_fft 2048 / hop 333, T 300: B 48 = 14 400 frames 145 M against 128 M it*frames/s for k_semi + k_ola,
       // B 32 = 9 600 frames 102 against 120: the crossover at n_fft 2048 is nearer 12 k; n_fft 1024 / hop 300 at 14 400: 260 vs 257)
-      long long hop_from = R >= 16 ? 12288 : 32768;
-      if (const char* e = getenv("SPECINV_SMALL_FRAMES")) hop_from = atoll(e);          // (tests: 0 pins the chunked kernels)
-      bool want_hop = R <= 16 && (long long)cfg.batch * cfg.n_frames >= hop_from && !small && cfg.hop_length >= 1 &&
-                      cfg.hop_length <= cfg.n_fft && pad < length;
-      if (const char* e = getenv("SPECINV_DISABLE_HOP")) {
-        if (e[0] == '1') want_hop = false;
-      }
+      const bool want_hop = !knobs.disable_hop && R <= 16 && n_all >= knobs.frames_from(R >= 16 ? 12288 : 32768) && !small &&
+                            cfg.hop_length >= 1 && cfg.hop_length <= cfg.n_fft && pad < length;
       if (want_hop) {
         const int floor_ch = std::max(8, (cfg.n_fft - 1) / cfg.hop_length + 1);
         // wave slots: one 8-wave workgroup per CU at n_fft 2048 (LDS), two at 1024, three at 512 (registers allow it)
-        long long slots = R >= 16 ? 2048 : R == 8 ? 4096 : 6144;
-        int best_nch = 1;
-        double best_cost = 1e300;
-        for (int nch = 1; nch <= std::max(1, cfg.n_frames / floor_ch); ++nch) {
-          const long long waves = (long long)cfg.batch * nch;
-          const long long rounds = (waves + slots - 1) / slots;
-          const int longest = (cfg.n_frames + nch - 1) / nch;
-          const double cost = (double)rounds * (longest + 2.0) * (1.0 + 0.0015 * std::max(0, longest - 32));
-          if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && nch > best_nch)) {
-            best_cost = cost;
-            best_nch = nch;
-          }
-        }
-        if (const char* e = getenv("SPECINV_FAST_CHUNK")) {
-          const int v = atoi(e);
-          if (v >= 1) best_nch = std::max(1, cfg.n_frames / std::min(std::max(v, floor_ch), cfg.n_frames));
-        }
+        const long long slots = R >= 16 ? 2048 : R == 8 ? 4096 : 6144;
         hopk = true;
-        nchunks = best_nch;
+        nchunks = pick_chunks(cfg.batch, cfg.n_frames, slots, 1, std::max(1, cfg.n_frames / floor_ch)).nch;
+        if (knobs.fast_chunk >= 1) nchunks = std::max(1, cfg.n_frames / std::min(std::max(knobs.fast_chunk, floor_ch), cfg.n_frames));
         chunk = (cfg.n_frames + nchunks - 1) / nchunks;
         n_waves = cfg.batch * nchunks;
-        if (getenv("SPECINV_DEBUG")) fprintf(stderr, "specinv: frame kernel with LDS overlap-add R=%d hop=%d chunks=%d of <=%d frames, %d waves\n", R, cfg.hop_length, nchunks, chunk, n_waves);
+        if (knobs.debug) fprintf(stderr, "specinv: frame kernel with LDS overlap-add R=%d hop=%d chunks=%d of <=%d frames, %d waves\n", R, cfg.hop_length, nchunks, chunk, n_waves);
       }
       return SPECINV_OK;
     }
-    // Frames per wave.  A launch takes about rounds x (longest chunk) frame times, rounds = ceil(waves / wave slots):
-    // pick the chunk count that minimises it (the chip holds 2 waves of these kernels per SIMD, 3 at n_fft 512, 1 at
-    // 4096), e.g. 64 x 1024 frames -> 32 chunks of 32 (2048 waves, one round), 96 x 1024 -> 21 chunks of 49 (2016 waves,
-    // one round) instead of 32 chunks (3072 waves, two rounds).  A chunk boundary costs OV - 1 split hop-blocks, and the
-    // reflected edge samples must not fall on split blocks (first / last chunk long enough): chunks of >= 8 (16) frames.
+    // Frames per wave: the chunk count that minimises chunk_cost (the chip holds 2 waves of these kernels per SIMD, 3 at n_fft
+    // 512, 1 at 4096).  A chunk boundary costs OV - 1 split hop-blocks, and the reflected edge samples must not fall on split
+    // blocks (first / last chunk long enough): chunks of >= 8 (16) frames.
     const int floor_ch = OV == 8 ? 16 : 8;
     long long slots = 1024LL * (R >= 32 ? 1 : R <= 4 ? 3 : 2);
     if (R == 8) slots = 1024LL * fast::kR8Waves;
@@ -235,55 +266,66 @@ struct FastState<float> {
     // workgroups leaves k CUs free.  For multi-GPU runs whose RCCL gather overlaps the next step's launches: an iteration
     // workgroup takes a whole CU's registers, so RCCL's workgroups can only run beside a launch that does not fill the chip
     // (bench.py --gather-kernel-budget; C2: 30 chunks of 34 frames on 240 CUs instead of 32 x 32 on 256: +6 % per launch).
-    if (const char* e = getenv("SPECINV_CU_BUDGET")) {
-      const int k = atoi(e);
-      if (k > 0 && k < 256) slots = slots * (256 - k) / 256;
-    }
-    int best_nch = 1;
-    double best_cost = 1e300;
-    for (int nch = 1; nch <= std::max(1, cfg.n_frames / floor_ch); ++nch) {
-      const long long waves = (long long)cfg.batch * nch;
-      const long long rounds = (waves + slots - 1) / slots;
-      const int longest = (cfg.n_frames + nch - 1) / nch;
-      // (+2: what a chunk boundary costs - split blocks, pipeline fill; measured: 2 rounds of 16-frame chunks are 8 %
-      // slower than 1 round of 32.  Last factor: chunks beyond 32 frames measured ~5 % slower than two rounds of 32)
-      const double cost = (double)rounds * (longest + 2.0) * (1.0 + 0.0015 * std::max(0, longest - 32));
-      if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && nch > best_nch)) {
-        best_cost = cost;
-        best_nch = nch;
-      }
-    }
+    if (knobs.cu_budget > 0 && knobs.cu_budget < 256) slots = slots * (256 - knobs.cu_budget) / 256;
+    const int most = std::max(1, cfg.n_frames / floor_ch);
+    ChunkPick best = pick_chunks(cfg.batch, cfg.n_frames, slots, 1, most);
     // The waves of a SIMD do not run at the same speed (begin_t: skewed chunks): where the skew applies - hop = n_fft/4 at n_fft
     // 2048 (chunk pairs) and 1024 (chunk triples) - a chunk count that pairs / triples up is preferred when it costs at most 4 %
-    // more frame times than the best one (round 5: B 65 or 100 at T 1024 took 31 / 20 chunks and ran unskewed)
+    // more frame times than the best one (round 5: B 65 or 100 at T 1024 took 31 / 20 chunks and ran unskewed); of two that cost
+    // the same, the smaller
     if (OV == 4 && (R == 16 || R == 8)) {
       const int mult = R == 16 ? 2 : 3;
-      auto cost_of = [&](int nch) {
-        const long long waves = (long long)cfg.batch * nch;
-        const long long rounds = (waves + slots - 1) / slots;
-        const int longest = (cfg.n_frames + nch - 1) / nch;
-        return (double)rounds * (longest + 2.0) * (1.0 + 0.0015 * std::max(0, longest - 32));
-      };
-      if (best_nch % mult != 0) {
-        int pick = 0;
-        double pick_cost = 1e300;
-        for (int nch = std::max(mult, best_nch - mult); nch <= std::min(best_nch + mult, std::max(1, cfg.n_frames / floor_ch)); ++nch)
-          if (nch % mult == 0 && cost_of(nch) < pick_cost) {
-            pick = nch;
-            pick_cost = cost_of(nch);
-          }
-        if (pick > 0 && pick_cost <= 1.04 * best_cost) best_nch = pick;
+      if (best.nch % mult != 0) {
+        const ChunkPick pick = pick_chunks(cfg.batch, cfg.n_frames, slots, std::max(mult, best.nch - mult), std::min(best.nch + mult, most), mult, 0.0);
+        if (pick.nch > 0 && pick.cost <= 1.04 * best.cost) best = pick;
       }
     }
-    nchunks = best_nch;
-    if (const char* e = getenv("SPECINV_FAST_CHUNK")) {
-      const int v = atoi(e);
-      if (v >= 4) nchunks = std::max(1, cfg.n_frames / std::min(std::max(v, OV == 8 ? 13 : 4), cfg.n_frames));
-    }
+    nchunks = best.nch;
+    if (knobs.fast_chunk >= 4) nchunks = std::max(1, cfg.n_frames / std::min(std::max(knobs.fast_chunk, OV == 8 ? 13 : 4), cfg.n_frames));
     chunk = (cfg.n_frames + nchunks - 1) / nchunks;   // frames split as evenly as possible (sizes differ by at most one)
     n_waves = cfg.batch * nchunks;
-    if (getenv("SPECINV_DEBUG")) fprintf(stderr, "specinv: fused R=%d OV=%d chunks=%d of <=%d frames, %d waves (%lld slots)\n", R, OV, nchunks, chunk, n_waves, slots);
+    if (knobs.debug) fprintf(stderr, "specinv: fused R=%d OV=%d chunks=%d of <=%d frames, %d waves (%lld slots)\n", R, OV, nchunks, chunk, n_waves, slots);
     supported = true;
+    return SPECINV_OK;
+  }
+
+  // The FastArgs fields every launch shares; a call site adds the signal and state pointers that are its own.  Every kernel gets
+  // all of them: k_semi never reads env, nchunks, n_waves or skew, the k_hop family reads its env from HopArgs and has no skew (it is
+  // 0 whenever `semi`: begin_t), k_fused_istft reads neither the target nor partials, pad_mode, coef and inv1p.
+  template <typename P>
+  fast::FastArgs base_args(P& pl) const {
+    fast::FastArgs a{};
+    a.m_pairs = mpairs.template as<v4f>();
+    a.m_mid = mmid.template as<float>();
+    if (two) {
+      a.P2_out = Pb2.template as<v4f>();
+      a.Pmid2_out = Pmid2.template as<v2f>();
+      a.m2_pairs = mpairs2.template as<v4f>();
+      a.m2_mid = mmid2.template as<float>();
+    }
+    a.window = pl.window.template as<float>();
+    a.env = pl.env.template as<float>();
+    a.partials = pl.partials.template as<double>();
+    a.T = pl.Tn();
+    a.nchunks = nchunks;
+    a.skew = skew;
+    a.n_waves = n_waves;
+    a.pad_mode = pl.cfg.pad_mode;
+    a.L = pl.length;
+    a.coef = pl.coef;
+    a.inv1p = 1.0f / (float)(1.0 + (double)pl.coef);
+    a.fwd_scale = pl.fc.fwd_scale;
+    a.inv_scale = pl.fc.inv_scale;
+    return a;
+  }
+
+  // fn(args) over `waves` waves: ceil(waves / wgw) workgroups of wgw waves, `lds` bytes of dynamic LDS each
+  template <typename P, typename A>
+  static int launch_waves(P& pl, const void* fn, const A& args, int waves, int wgw, size_t lds) {
+    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    A copy = args;
+    void* kargs[] = {&copy};
+    SI_HIP(hipLaunchKernel(fn, dim3((waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
     return SPECINV_OK;
   }
 
@@ -296,7 +338,7 @@ struct FastState<float> {
     mode = md;
     // (n_fft 4096 runs one wave per SIMD: its vector latency, not the state traffic, is what bounds it there - the signal form
     // measured 0.360 against 0.340 ms per iteration and is not used)
-    td = md == fast::MODE_GLA && (!semi || hopk) && !use_template && !keep_state && RR <= 16 && !two;
+    td = md == fast::MODE_GLA && (!semi || hopk) && !knobs.fused_template && !keep_state && RR <= 16 && !two;
     // (the signal-form kernels leave the real-FFT split unscaled, which is exact only for a power-of-two fwd_scale / 2)
     if (pl.cfg.normalized && !hopk) td = false;
     // k_hop_td writes two signals and re-reads z_t where k_hop writes one: at large hops its emission loop overtakes the saved state
@@ -323,6 +365,7 @@ struct FastState<float> {
     // of a workgroup share a SIMD whatever the number of workgroups or rounds, so the pairing holds for any launch that puts two
     // waves on a SIMD (more waves than SIMDs); the skew scales with the chunk: a quarter of its frames (10 of 32 at C2), the
     // shorter chunk keeping >= 8 (the floor of a chunk: its seams).
+    // (every rule below asks for !semi: the frame kernels, k_hop's chunks included, always run with skew = 0)
     skew = 0;
     {
       const int len_ch = pl.Tn() / std::max(1, nchunks);
@@ -334,7 +377,7 @@ struct FastState<float> {
       // ... and the n_fft 1024 kernels (spectral state or signal form) at three waves per SIMD (12-wave workgroups, the hardware
       // slot is the wave's index in the workgroup / 4, kernels_fused.h): chunk triples, the oldest wave the longest.  BASELINE
       // C4's shard: 3072 waves, chunks of 64 frames, begin shifts 4 / 6; other chunk lengths scale them.
-      if (!semi && RR == 8 && OV == 4 && !use_template && fused_wgw() == 12 && nchunks % 3 == 0 && len_ch >= 16) {
+      if (!semi && RR == 8 && OV == 4 && !knobs.fused_template && fused_wgw() == 12 && nchunks % 3 == 0 && len_ch >= 16) {
         // (C4 step, two runs each: "0,0" 30.38 / 30.38 ms, "3,4" 30.29 / 30.26, "4,6" 29.93 / 29.97, "5,8" 30.49 / 30.20, "6,9"
         // 30.27 / 30.21: the kernel sits on the memory system, the balance buys 1.4 %)
         constexpr int kSkew1 = 4, kSkew2 = 6;
@@ -343,14 +386,14 @@ struct FastState<float> {
         if ((s1 | s2) && len_ch - s2 >= 8 && len_ch + s2 - s1 >= 8) skew = 0x10000 | (s1 << 8) | s2;
       }
     }
-    if (const char* e = getenv("SPECINV_K4_SKEW")) {          // "s1,s2" (experiments; "0,0" switches it off)
-      int s1 = 0, s2 = 0;
-      if (sscanf(e, "%d,%d", &s1, &s2) == 2 && !semi && fused_wgw() == 12 && nchunks % 3 == 0 && n_waves % 12 == 0 && s1 >= 0 && s2 >= 0 &&
-          s1 < 200 && s2 < 200 && pl.Tn() / nchunks - s2 >= 8 && pl.Tn() / nchunks + s2 - s1 >= 8)
+    if (knobs.has_k4_skew) {
+      const int s1 = knobs.k4_s1, s2 = knobs.k4_s2;
+      if (!semi && fused_wgw() == 12 && nchunks % 3 == 0 && n_waves % 12 == 0 && s1 >= 0 && s2 >= 0 && s1 < 200 && s2 < 200 &&
+          pl.Tn() / nchunks - s2 >= 8 && pl.Tn() / nchunks + s2 - s1 >= 8)
         skew = (s1 | s2) ? (0x10000 | (s1 << 8) | s2) : 0;
     }
-    if (const char* e = getenv("SPECINV_TD_SKEW")) {
-      const int v = atoi(e);
+    if (knobs.has_td_skew) {
+      const int v = knobs.td_skew;
       if (v == 0 || (td && !semi && (nchunks & 1) == 0 && (n_waves & 1) == 0 && pl.Tn() / nchunks - v >= 8)) skew = v;
     }
     if (td) {
@@ -361,13 +404,12 @@ struct FastState<float> {
     const size_t pbytes = (size_t)nf * G::H * 64 * sizeof(v4f);
     const size_t tail_bytes = (size_t)pl.B() * nchunks * (OV > 0 ? OV - 1 : 0) * hop * sizeof(float);
     if (hopk) SI_TRY(xtail[0].reserve((size_t)pl.B() * nchunks * (pl.N() - hop) * sizeof(float) + 16));
-    for (int i = 0; i < ((semi && !hopk) ? 1 : 2); ++i) {     // x (and the chunk tails) ping-pong between iterations
+    for (int i = 0; i < ((semi && !hopk) ? 1 : 2); ++i) {     // (k_semi + k_ola rewrite x in place)
       if (!semi) SI_TRY(xtail[i].reserve(tail_bytes));
       SI_TRY(xb[i].reserve((size_t)pl.B() * pl.length * sizeof(float)));
-      if (i == 1 && state_in_place) continue;      // the spectral state is updated in place
-      SI_TRY(Pb[i].reserve(pbytes));
-      SI_TRY(Pmid[i].reserve(nf * sizeof(v2f)));
     }
+    SI_TRY(Pb.reserve(pbytes));
+    SI_TRY(Pmid.reserve(nf * sizeof(v2f)));
     if (semi && !hopk) SI_TRY(pl.frames_needed());
     SI_TRY(mpairs.reserve((size_t)nf * (G::H / 2) * 64 * sizeof(v4f)));
     SI_TRY(mmid.reserve(nf * sizeof(float)));
@@ -386,8 +428,8 @@ struct FastState<float> {
       const void* fn = (const void*)fast::k_phase_init_pairs<RR>;
       SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const float* mg = mag_user;
-      v4f* pp = Pb[0].template as<v4f>();
-      v2f* pm = Pmid[0].template as<v2f>();
+      v4f* pp = Pb.template as<v4f>();
+      v2f* pm = Pmid.template as<v2f>();
       float* mp = mpairs.template as<float>();
       float* mm = mmid.template as<float>();
       double* part = pl.partials.template as<double>();
@@ -401,8 +443,8 @@ struct FastState<float> {
     } else {
       const int rows = pl.n_freq;                   // G::M + 1, or N for a two-sided spectrogram
       const dim3 grid((pl.Tn() + 31) / 32, (G::M + 1 + 31) / 32, pl.B()), blk(32, 8);
-      hipLaunchKernelGGL((fast::k_user_spec_to_pairs<RR>), grid, blk, 0, pl.stream, spec_user, Pb[0].template as<v2f>(),
-                         Pmid[0].template as<v2f>(), pl.Tn(), rows, 0);
+      hipLaunchKernelGGL((fast::k_user_spec_to_pairs<RR>), grid, blk, 0, pl.stream, spec_user, Pb.template as<v2f>(),
+                         Pmid.template as<v2f>(), pl.Tn(), rows, 0);
       SI_HIP(hipGetLastError());
       const long long nblk1 = (long long)grid.x * grid.y * grid.z, nblk = two ? 2 * nblk1 : nblk1;
       SI_TRY(pl.partials.reserve(std::max<size_t>((size_t)nblk, 3 * 1024) * sizeof(double)));
@@ -424,8 +466,8 @@ struct FastState<float> {
     xu_valid = false;
     if (md == fast::MODE_ADMM && keep_state) {      // methods.py:447-449: X = the start spectrum, U = 0 (Y = X is already in Pb)
       SI_TRY(reserve_xu(pl));
-      SI_HIP(hipMemcpyAsync(Xb.p, Pb[0].p, pbytes, hipMemcpyDeviceToDevice, pl.stream));
-      SI_HIP(hipMemcpyAsync(Xmid.p, Pmid[0].p, nf * sizeof(v2f), hipMemcpyDeviceToDevice, pl.stream));
+      SI_HIP(hipMemcpyAsync(Xb.p, Pb.p, pbytes, hipMemcpyDeviceToDevice, pl.stream));
+      SI_HIP(hipMemcpyAsync(Xmid.p, Pmid.p, nf * sizeof(v2f), hipMemcpyDeviceToDevice, pl.stream));
       SI_HIP(hipMemsetAsync(Ub.p, 0, pbytes, pl.stream));
       SI_HIP(hipMemsetAsync(Umid.p, 0, nf * sizeof(v2f), pl.stream));
       xu_valid = true;
@@ -441,20 +483,10 @@ struct FastState<float> {
     }
     SI_HIP(hipMemsetAsync(xtail[0].p, 0, tail_bytes, pl.stream));   // x0 below is written whole
     // x0 = ISTFT(start spectrum) (methods.py:233 / :453) straight from the pair layout
-    fast::FastArgs a{};
+    fast::FastArgs a = base_args(pl);
     a.x_out = xb[0].template as<float>();
-    a.P_in = Pb[0].template as<v4f>();
-    a.Pmid_in = Pmid[0].template as<v2f>();
-    a.window = pl.window.template as<float>();
-    a.env = pl.env.template as<float>();
-    a.T = pl.Tn();
-    a.nchunks = nchunks;
-    a.skew = skew;
-    a.n_waves = n_waves;
-    a.L = pl.length;
-    a.fwd_scale = pl.fc.fwd_scale;
-    a.inv_scale = pl.fc.inv_scale;
-    const size_t lds = G::lds_bytes(4);
+    a.P_in = Pb.template as<v4f>();
+    a.Pmid_in = Pmid.template as<v2f>();
     const void* fn = nullptr;
     if constexpr (RR % 8 == 0) {
       if (OV == 8) fn = (const void*)fast::k_fused_istft<RR, 8>;
@@ -462,9 +494,7 @@ struct FastState<float> {
     if (OV == 4) fn = (const void*)fast::k_fused_istft<RR, 4>;
     if (OV == 2) fn = (const void*)fast::k_fused_istft<RR, 2>;
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* kargs[] = {&a};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_waves + 3) / 4), dim3(256), kargs, lds, pl.stream));
+    SI_TRY(launch_waves(pl, fn, a, n_waves, 4, G::lds_bytes(4)));
     SI_HIP(hipStreamSynchronize(pl.stream));   // *sum_m2_out is valid from here on
     return SPECINV_OK;
   }
@@ -514,13 +544,9 @@ struct FastState<float> {
   template <typename P>
   int launch_inverse_ola(P& pl, const fast::v2f* spec, float* out, long long len, float scale, float** margins, bool* used) {
     *used = false;
-    if (!xform_ok || xform_R > 16 || pl.force_generic) return SPECINV_OK;
+    if (!xform_ok || xform_R > 16 || pl.force_generic || knobs.disable_hop) return SPECINV_OK;
     const int N = pl.N(), hop = pl.cfg.hop_length, T = pl.Tn(), B = pl.B();
-    long long from = xform_R >= 16 ? 16384 : 32768;
-    if (const char* e = getenv("SPECINV_SMALL_FRAMES")) from = atoll(e);
-    if (const char* e = getenv("SPECINV_DISABLE_HOP")) {
-      if (e[0] == '1') return SPECINV_OK;
-    }
+    const long long from = knobs.frames_from(xform_R >= 16 ? 16384 : 32768);
     if ((long long)B * T < from || hop < 1 || hop > N || pl.pad >= len) return SPECINV_OK;
     // the kernel writes every sample of `out` only if the frames cover the padded signal exactly
     if ((long long)(T - 1) * hop + N != len + 2LL * pl.pad) return SPECINV_OK;
@@ -549,9 +575,7 @@ struct FastState<float> {
       fn = (const void*)fast::k_hop_inverse<RR>;
     });
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no k_hop_inverse instantiation");
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* kargs[] = {&a};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_w + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
+    SI_TRY(launch_waves(pl, fn, a, n_w, wgw, lds));
     if (nch > 1 && keep > 0) {
       const long long total = (long long)B * (nch - 1) * keep;
       hipLaunchKernelGGL(fast::k_hop_tails_raw, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, pl.stream, out,
@@ -562,12 +586,12 @@ struct FastState<float> {
     *used = true;
     return SPECINV_OK;
   }
-  FastBuf hop_inv_tail, hop_inv_margins;
+  DevBuf hop_inv_tail, hop_inv_margins;
 
   // waves per workgroup of the fused iteration kernel: k_fused4 takes 8-wave workgroups (one per CU) once every wave
   // slot is filled; fewer waves than slots: smaller workgroups reach more CUs
   int fused_wgw() const {
-    if (R == 8 && OV == 4 && !use_template) {
+    if (R == 8 && OV == 4 && !knobs.fused_template) {
       // three waves per SIMD: a 12-wave workgroup is a whole CU, and 8-wave workgroups do not pair up there (2 + 2 waves on a SIMD
       // that holds 3: at 2048 ... 3071 waves every CU's second workgroup waited for the first - round 5's sweep, B 64 x T 300:
       // 316 M against 400 M at B 48).  Below a full chip, 4-wave workgroups: three fit a CU.
@@ -579,17 +603,18 @@ struct FastState<float> {
     // the workgroup / 4, whatever else runs on the chip - the 4-wave form has to infer it from the dispatch order (measured with
     // the skew: 19.89-20.09 against 20.02-20.16 ms per C2 step, tools/log/EXPERIMENTS.md r03 wgw8)
     if (td && R == 16 && OV == 4) return (skew != 0 && skew < 0x10000) ? 8 : 4;
-    if ((R == 8 || R == 16) && OV == 4 && !use_template) return n_waves >= 2048 ? fast::kFused4Waves : 4;
+    if ((R == 8 || R == 16) && OV == 4 && !knobs.fused_template) return n_waves >= 2048 ? fast::kFused4Waves : 4;
     return 4;
   }
-  // {waves per workgroup, chunks per item, waves, kernel: 1 k_fused4, 2 k_fused<R, OV>, 3 k_semi, 4 k_hop, 5 k_fused_td<R, 4> at n_fft 1024 / 2048, 6 k_fused_td<R, OV> otherwise}
+  // {waves per workgroup, chunks per item, waves, kernel (FastKernel)}
   void geometry(int out[4]) const {
     if (semi) {
       out[0] = hopk ? 8 : 4;
-      out[3] = hopk ? (td ? 7 : 4) : 3;
+      out[3] = hopk ? (td ? kKernelHopTd : kKernelHop) : kKernelSemi;
     } else {
+      const bool tuned = (R == 8 || R == 16) && OV == 4 && !knobs.fused_template;
       out[0] = fused_wgw();
-      out[3] = ((R == 8 || R == 16) && OV == 4 && !use_template) ? (td ? 5 : 1) : (td ? 6 : 2);
+      out[3] = tuned ? (td ? kKernelFused4Td : kKernelFused4) : (td ? kKernelFusedTd : kKernelFused);
     }
     out[1] = nchunks;
     out[2] = n_waves;
@@ -597,38 +622,22 @@ struct FastState<float> {
 
   template <int RR, int MODE, bool EVAL, typename P>
   int launch(P& pl, const fast::FastArgs& a) {
-    using G = fast::Geo<RR>;
     const void* fn = nullptr;
     if constexpr (RR % 8 == 0) {
       if (OV == 8) fn = (const void*)fast::k_fused<RR, 8, MODE, EVAL>;
     }
     if constexpr (RR == 8 || RR == 16) {
       if (OV == 4)                                                       // the tuned copy for the headline shapes
-        fn = use_template ? (const void*)fast::k_fused<RR, 4, MODE, EVAL> : (const void*)fast::k_fused4<RR, MODE, EVAL>;
+        fn = knobs.fused_template ? (const void*)fast::k_fused<RR, 4, MODE, EVAL> : (const void*)fast::k_fused4<RR, MODE, EVAL>;
     } else {
       if (OV == 4) fn = (const void*)fast::k_fused<RR, 4, MODE, EVAL>;
     }
     if (OV == 2) fn = (const void*)fast::k_fused<RR, 2, MODE, EVAL>;
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
     const int wgw = fused_wgw();
-    const size_t lds_used = G::lds_bytes(wgw);
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
-    fast::FastArgs args = a;
-    void* kargs[] = {&args};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds_used, pl.stream));
-    return SPECINV_OK;
+    return launch_waves(pl, fn, a, n_waves, wgw, fast::Geo<RR>::lds_bytes(wgw));
   }
 
-  template <int RR, int OVV>
-  static const void* td_kernel(bool early, bool ev) {
-    return early ? (ev ? (const void*)fast::k_fused_td<RR, OVV, true, true> : (const void*)fast::k_fused_td<RR, OVV, true, false>)
-                 : (ev ? (const void*)fast::k_fused_td<RR, OVV, false, true> : (const void*)fast::k_fused_td<RR, OVV, false, false>);
-  }
-  template <int RR>
-  static const void* td_kernel4(bool early, bool ev) {
-    return early ? (ev ? (const void*)fast::k_fused4_td<RR, true, true> : (const void*)fast::k_fused4_td<RR, true, false>)
-                 : (ev ? (const void*)fast::k_fused4_td<RR, false, true> : (const void*)fast::k_fused4_td<RR, false, false>);
-  }
   template <typename P>
   int launch_td(P& pl, const fast::FastArgs& a, bool early, bool ev) {
     const void* fn = nullptr;
@@ -636,17 +645,13 @@ struct FastState<float> {
     const int wgw = fused_wgw();
     SPECINV_R_SWITCH(R, if constexpr (RR <= 16) {                      // (n_fft 4096 never takes the signal form: begin_t)
                        lds_used = fast::Geo<RR>::lds_bytes_td(wgw);
-                       if constexpr (RR % 8 == 0) { if (OV == 8) fn = td_kernel<RR, 8>(early, ev); }
-                       if constexpr (RR == 8 || RR == 16) { if (OV == 4) fn = td_kernel4<RR>(early, ev); }
-                       else { if (OV == 4) fn = td_kernel<RR, 4>(early, ev); }
-                       if (OV == 2) fn = td_kernel<RR, 2>(early, ev);
+                       if constexpr (RR % 8 == 0) { if (OV == 8) fn = SPECINV_EARLY_EVAL(early, ev, fast::k_fused_td, RR, 8); }
+                       if constexpr (RR == 8 || RR == 16) { if (OV == 4) fn = SPECINV_EARLY_EVAL(early, ev, fast::k_fused4_td, RR); }
+                       else { if (OV == 4) fn = SPECINV_EARLY_EVAL(early, ev, fast::k_fused_td, RR, 4); }
+                       if (OV == 2) fn = SPECINV_EARLY_EVAL(early, ev, fast::k_fused_td, RR, 2);
                      });
     SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
-    fast::FastArgs args = a;
-    void* kargs[] = {&args};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds_used, pl.stream));
-    return SPECINV_OK;
+    return launch_waves(pl, fn, a, n_waves, wgw, lds_used);
   }
 
   template <int RR, int MODE, bool EVAL, typename P>
@@ -654,27 +659,11 @@ struct FastState<float> {
     using G = fast::Geo<RR>;
     fast::SemiArgs s{};
     fast::FastArgs& a = s.f;
+    a = base_args(pl);
     a.x_in = xb[0].template as<float>();
-    a.P_out = Pb[0].template as<v4f>();
-    a.Pmid_out = Pmid[0].template as<v2f>();
+    a.P_out = Pb.template as<v4f>();
+    a.Pmid_out = Pmid.template as<v2f>();
     if (MODE == fast::MODE_ADMM) SI_TRY(want_xu(pl, a, last));
-    a.m_pairs = mpairs.template as<v4f>();
-    a.m_mid = mmid.template as<float>();
-    if (two) {
-      a.P2_out = Pb2.template as<v4f>();
-      a.Pmid2_out = Pmid2.template as<v2f>();
-      a.m2_pairs = mpairs2.template as<v4f>();
-      a.m2_mid = mmid2.template as<float>();
-    }
-    a.window = pl.window.template as<float>();
-    a.partials = pl.partials.template as<double>();
-    a.T = pl.Tn();
-    a.pad_mode = pl.cfg.pad_mode;
-    a.L = pl.length;
-    a.coef = pl.coef;
-    a.inv1p = 1.0f / (float)(1.0 + (double)pl.coef);
-    a.fwd_scale = pl.fc.fwd_scale;
-    a.inv_scale = pl.fc.inv_scale;
     s.frames = pl.frames.template as<float>();
     s.n_frames_total = (long long)pl.B() * pl.Tn();
     s.hop = pl.cfg.hop_length;
@@ -695,39 +684,18 @@ struct FastState<float> {
     const int nx = MODE == fast::MODE_INIT ? 0 : (cur ^ 1);
     fast::HopArgs s{};
     fast::FastArgs& a = s.f;
+    a = base_args(pl);
     a.x_in = xb[cur].template as<float>();
     a.x_out = xb[nx].template as<float>();
-    a.P_out = Pb[0].template as<v4f>();
-    a.Pmid_out = Pmid[0].template as<v2f>();
+    a.P_out = Pb.template as<v4f>();
+    a.Pmid_out = Pmid.template as<v2f>();
     if (MODE == fast::MODE_ADMM) SI_TRY(want_xu(pl, a, last));
-    a.m_pairs = mpairs.template as<v4f>();
-    a.m_mid = mmid.template as<float>();
-    a.window = pl.window.template as<float>();
-    a.partials = pl.partials.template as<double>();
-    a.T = pl.Tn();
-    a.nchunks = nchunks;
-    a.n_waves = n_waves;
-    a.pad_mode = pl.cfg.pad_mode;
-    a.L = pl.length;
-    a.coef = pl.coef;
-    a.inv1p = 1.0f / (float)(1.0 + (double)pl.coef);
-    a.fwd_scale = pl.fc.fwd_scale;
-    a.inv_scale = pl.fc.inv_scale;
-    if (two) {
-      a.P2_out = Pb2.template as<v4f>();
-      a.Pmid2_out = Pmid2.template as<v2f>();
-      a.m2_pairs = mpairs2.template as<v4f>();
-      a.m2_mid = mmid2.template as<float>();
-    }
-    s.env = pl.env.template as<float>();
+    s.env = a.env;
     s.xtail = xtail[0].template as<float>();
     s.hop = hop;
     s.pad = pl.pad;
-    const size_t lds = G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float);
     const void* fn = two ? (const void*)fast::k_hop2<RR, MODE, EVAL> : (const void*)fast::k_hop<RR, MODE, EVAL>;
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* kargs[] = {&s};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
+    SI_TRY(launch_waves(pl, fn, s, n_waves, wgw, G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float)));
     if (nchunks > 1 && keep > 0) {
       const long long total = (long long)pl.B() * (nchunks - 1) * keep;
       hipLaunchKernelGGL(fast::k_hop_tails, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, pl.stream, a.x_out,
@@ -747,39 +715,24 @@ struct FastState<float> {
     const int nx = cur ^ 1;
     ++td_t;
     const double tds = std::pow(-(double)pl.coef, (double)td_t);
-    const bool early = std::fabs(tds) >= 9.3132257461547852e-10;       // 2^-30, as in iterate()
+    const bool early = std::fabs(tds) >= fast::kTdsFloor;
     fast::HopArgs s{};
     fast::FastArgs& a = s.f;
+    a = base_args(pl);
     a.x_in = td_t == 1 ? xb[cur].template as<float>() : zb[cur].template as<float>();
     a.x_out = zb[nx].template as<float>();
     a.x2_in = xb[cur].template as<float>();
     a.x2_out = xb[nx].template as<float>();
-    a.P_in = Pb[0].template as<v4f>();
-    a.Pmid_in = Pmid[0].template as<v2f>();
+    a.P_in = Pb.template as<v4f>();
+    a.Pmid_in = Pmid.template as<v2f>();
     a.tds = (float)tds;
-    a.m_pairs = mpairs.template as<v4f>();
-    a.m_mid = mmid.template as<float>();
-    a.window = pl.window.template as<float>();
-    a.partials = pl.partials.template as<double>();
-    a.T = pl.Tn();
-    a.nchunks = nchunks;
-    a.n_waves = n_waves;
-    a.pad_mode = pl.cfg.pad_mode;
-    a.L = pl.length;
-    a.coef = pl.coef;
-    a.fwd_scale = pl.fc.fwd_scale;
-    a.inv_scale = pl.fc.inv_scale;
-    s.env = pl.env.template as<float>();
+    s.env = a.env;
     s.xtail = xtail[0].template as<float>();
     s.hop = hop;
     s.pad = pl.pad;
     s.write_x = need_x ? 1 : 0;
-    const size_t lds = G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float);
-    const void* fn = early ? (ev ? (const void*)fast::k_hop_td<RR, true, true> : (const void*)fast::k_hop_td<RR, true, false>)
-                           : (ev ? (const void*)fast::k_hop_td<RR, false, true> : (const void*)fast::k_hop_td<RR, false, false>);
-    SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* kargs[] = {&s};
-    SI_HIP(hipLaunchKernel(fn, dim3((n_waves + wgw - 1) / wgw), dim3(64 * wgw), kargs, lds, pl.stream));
+    const void* fn = SPECINV_EARLY_EVAL(early, ev, fast::k_hop_td, RR);
+    SI_TRY(launch_waves(pl, fn, s, n_waves, wgw, G::lds_bytes(wgw) + (size_t)wgw * G::N * sizeof(float)));
     if (nchunks > 1 && keep > 0) {
       const long long total = (long long)pl.B() * (nchunks - 1) * keep;
       hipLaunchKernelGGL(fast::k_hop_tails_td, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, pl.stream, a.x2_out, a.x_out,
@@ -821,65 +774,40 @@ struct FastState<float> {
     SI_TRY(pl.partials.reserve(std::max<size_t>((size_t)n_waves * 2 * fast::kEvalPieces, 3 * 1024) * sizeof(double)));
     int eval_pieces = 1;
     for (int i = 0; i < n_iter; ++i) {
-      const bool ev = eval_last && i == n_iter - 1;
+      const bool last = i == n_iter - 1, ev = eval_last && last;
       const int nx = cur ^ 1;
-      fast::FastArgs a{};
+      fast::FastArgs a = base_args(pl);
       a.x_in = xb[cur].template as<float>();
       a.x_out = xb[nx].template as<float>();
       a.xtail_in = xtail[cur].template as<float>();
       a.xtail_out = xtail[nx].template as<float>();
-      // the spectral state of a frame is read and written by the same lane: it can live in one buffer
-      const int ps = state_in_place ? 0 : cur, pn = state_in_place ? 0 : nx;
-      a.P_in = Pb[ps].template as<v4f>();
-      a.P_out = Pb[pn].template as<v4f>();
-      a.Pmid_in = Pmid[ps].template as<v2f>();
-      a.Pmid_out = Pmid[pn].template as<v2f>();
-      SI_TRY(want_xu(pl, a, i == n_iter - 1));
-      a.m_pairs = mpairs.template as<v4f>();
-      a.m_mid = mmid.template as<float>();
-      a.window = pl.window.template as<float>();
-      a.env = pl.env.template as<float>();
-      a.partials = pl.partials.template as<double>();
-      a.T = pl.Tn();
-        a.nchunks = nchunks;
-      a.skew = skew;
-      a.n_waves = n_waves;
-      a.pad_mode = pl.cfg.pad_mode;
-      a.L = pl.length;
-      a.coef = pl.coef;
-      a.inv1p = 1.0f / (float)(1.0 + (double)pl.coef);
-      a.fwd_scale = pl.fc.fwd_scale;
-      a.inv_scale = pl.fc.inv_scale;
+      a.P_in = Pb.template as<v4f>();          // (the signal form: the starting spectrum c0)
+      a.P_out = Pb.template as<v4f>();
+      a.Pmid_in = Pmid.template as<v2f>();
+      a.Pmid_out = Pmid.template as<v2f>();
+      SI_TRY(want_xu(pl, a, last));
       if (td) {
         ++td_t;
         const double tds = std::pow(-(double)pl.coef, (double)td_t);
-        const bool early = std::fabs(tds) >= 9.3132257461547852e-10;       // 2^-30: below float32 resolution of |pre|
+        const bool early = std::fabs(tds) >= fast::kTdsFloor;
         a.x_in = td_t == 1 ? xb[cur].template as<float>() : zb[cur].template as<float>();
         a.x_out = zb[nx].template as<float>();
         a.x2_in = xb[cur].template as<float>();
         // x_{t+1} has a reader only after the last iteration of a call (get_wave, the next call) and before an evaluating launch
-        const bool need_x = i == n_iter - 1 || (eval_last && i == n_iter - 2);
+        const bool need_x = last || (eval_last && i == n_iter - 2);
         a.x2_out = need_x ? xb[nx].template as<float>() : nullptr;
-        a.P_in = Pb[0].template as<v4f>();
-        a.Pmid_in = Pmid[0].template as<v2f>();
         a.tds = (float)tds;
         // an evaluating iteration on the headline shapes: the plain kernel, then the evaluation of x_t as a kernel of its own
         // (kernels_fast_td.h: k_eval_td; SPECINV_EVAL_KERNEL=0: the fused evaluating variant)
-        const char* eval_env = ev ? getenv("SPECINV_EVAL_KERNEL") : nullptr;
-        const bool eval_kernel = !(eval_env && eval_env[0] == '0');
-        if (ev && eval_kernel && OV == 4 && (R == 8 || R == 16)) {
+        if (ev && knobs.eval_kernel && OV == 4 && (R == 8 || R == 16)) {
           SI_TRY(launch_td(pl, a, early, false));
           const void* fn = R == 16 ? (const void*)fast::k_eval_td<16, 4> : (const void*)fast::k_eval_td<8, 4>;
           const size_t lds_used = R == 16 ? fast::Geo<16>::lds_bytes(4) : fast::Geo<8>::lds_bytes(4);
-          SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_used));
-          fast::FastArgs args = a;
-          void* kargs[] = {&args};
-          SI_HIP(hipLaunchKernel(fn, dim3((n_waves * fast::kEvalPieces + 3) / 4), dim3(256), kargs, lds_used, pl.stream));
+          SI_TRY(launch_waves(pl, fn, a, n_waves * fast::kEvalPieces, 4, lds_used));
           eval_pieces = fast::kEvalPieces;
-          cur = nx;
-          continue;
+        } else {
+          SI_TRY(launch_td(pl, a, early, ev));
         }
-        SI_TRY(launch_td(pl, a, early, ev));
         cur = nx;
         continue;
       }
@@ -919,15 +847,14 @@ struct FastState<float> {
   int get_state_spec(P& pl, int which, cplx<float>* out) {
     const long long nf = (long long)pl.B() * pl.Tn();
     SI_TRY(scratch.reserve((size_t)nf * pl.n_freq * sizeof(v2f)));
-    const int ps = (semi || state_in_place) ? 0 : cur;
     const bool admm = mode == fast::MODE_ADMM;
     SI_CHECK(admm || !td || td_t == 0, SPECINV_ESTATE,
              "Griffin-Lim carries its momentum as a signal on this path (pre_spec is never formed); call "
              "specinv_plan_keep_state(plan, 1) before specinv_gla_init to iterate on pre_spec itself");
     SI_CHECK(!admm || which == 2 || xu_valid, SPECINV_ESTATE,
              "ADMM carries Y = X + U; call specinv_plan_keep_state(plan, 1) before iterating to read X and U (which = 2 reads Y)");
-    const FastBuf& src = (!admm || which == 2) ? Pb[ps] : which == 0 ? Xb : Ub;
-    const FastBuf& mid = (!admm || which == 2) ? Pmid[ps] : which == 0 ? Xmid : Umid;
+    const DevBuf& src = (!admm || which == 2) ? Pb : which == 0 ? Xb : Ub;
+    const DevBuf& mid = (!admm || which == 2) ? Pmid : which == 0 ? Xmid : Umid;
     SI_CHECK(!two || !admm || which == 2, SPECINV_EUNSUPPORTED, "X and U of a two-sided ADMM run are not kept on this path");
     SPECINV_R_SWITCH(R, const long long np = nf * fast::Geo<RR>::H * 64;
                      hipLaunchKernelGGL((fast::k_pairs_to_spec<RR>), dim3((unsigned)ceil_div(np, 256)), dim3(256), 0, pl.stream,

@@ -640,15 +640,15 @@ struct LbfgsDev {
   LbdState h{};                           // host mirror (valid after a step)
   int64_t n = 0;                          // elements of x
   int par = 0;                            // which of the two state records is current
-  FastBuf st, sgp, ygp, rho, sy, yy, coef, lin_ptr, dot_ptr, ys_slot, ss_slot, rows, mpart;
+  DevBuf st, sgp, ygp, rho, sy, yy, coef, lin_ptr, dot_ptr, ys_slot, ss_slot, rows, mpart;
   // the parameter-sized vectors (two gradients, the direction, the ring of curvature pairs) come from - and go back to - a pool
   // the plan keeps: an optimiser is created per L_BFGS call, and 2 (history + 1) + 3 hipMallocs of the parameter's size per call
   // would cost more than the step they serve
-  std::vector<std::unique_ptr<FastBuf>> vecs;
+  std::vector<std::unique_ptr<DevBuf>> vecs;
   T* g0 = nullptr;
   T* g1 = nullptr;
   T* d = nullptr;
-  FastBuf ticket;                         // the two-launch lean iteration: workgroups of the epilogue done (fast::ObjDecide)
+  DevBuf ticket;                         // the two-launch lean iteration: workgroups of the epilogue done (fast::ObjDecide)
   T* x_user = nullptr;                    // the caller's iterate (set per step) and the optimiser's second buffer (deferred step)
   T* x_alt = nullptr;
   std::vector<T*> pairs_y, pairs_s;       // host mirror of the slot tables (allocated so far)
@@ -697,7 +697,7 @@ struct LbfgsDev {
 template <typename P>
 int lbd_take(P& pl, LbfgsDev<float>& L, float** out) {
   const size_t bytes = (size_t)L.n * sizeof(float);
-  std::unique_ptr<FastBuf> b;
+  std::unique_ptr<DevBuf> b;
   for (size_t i = 0; i < pl.lbd_pool.size(); ++i)
     if (pl.lbd_pool[i]->bytes >= bytes) {
       b = std::move(pl.lbd_pool[i]);
@@ -705,7 +705,7 @@ int lbd_take(P& pl, LbfgsDev<float>& L, float** out) {
       break;
     }
   if (!b) {
-    b.reset(new FastBuf());
+    b.reset(new DevBuf());
     SI_TRY(b->reserve(bytes));
   }
   *out = b->template as<float>();

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <vector>
 
+#include "dev_buf.h"
 #include "kernels_adjoint.h"
 #include "fast_state.h"
 #include "kernels_generic.h"
@@ -19,39 +20,6 @@
 #include "plan.h"
 
 namespace specinv {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) {
-      (void)hipFree(p);
-      account_bytes(-(int64_t)bytes);
-    }
-    p = nullptr;
-    bytes = 0;
-  }
-  // grow-only allocation
-  int reserve(size_t n) {
-    if (n <= bytes && p) return SPECINV_OK;
-    release();
-    if (n == 0) n = 16;
-    hipError_t e = hipMalloc(&p, n);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return fail(SPECINV_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(e));
-    }
-    bytes = n;
-    account_bytes((int64_t)n);
-    return SPECINV_OK;
-  }
-  template <typename U>
-  U* as() const { return static_cast<U*>(p); }
-};
 
 // radix schedule of the LDS Stockham FFT: powers of two as 8s and 4s (fewest stages), then 3, 5, 7, other primes
 inline std::vector<int> factorize(int n) {
@@ -1103,7 +1071,7 @@ struct PlanT final : PlanBase {
 
   // the device-resident optimiser (lbfgs_dev.h): float32 on the one-launch objective
   std::vector<std::unique_ptr<LbfgsDev<float>>> lbfgs_devs;
-  std::vector<std::unique_ptr<FastBuf>> lbd_pool;     // parameter-sized vectors of optimisers that are gone, for the next one
+  std::vector<std::unique_ptr<DevBuf>> lbd_pool;     // parameter-sized vectors of optimisers that are gone, for the next one
   static constexpr size_t kLbdPoolKeep = 4 + 2 * 11;  // (what an optimiser at main.py:43's history_size = 10 needs)
   int lbfgs_dev_create(int64_t n, const specinv_lbfgs_opts* opts, int32_t* handle_out) override {
     SI_CHECK(opts && handle_out, SPECINV_EINVAL, "null pointer");

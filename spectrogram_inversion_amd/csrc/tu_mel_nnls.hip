@@ -1,6 +1,7 @@
 // k_mel_nnls (kernels_mel_nnls.h) and the plan state behind specinv_mel_nnls_setup / specinv_mel_nnls.
 #include <mutex>
 
+#include "dev_buf.h"
 #include "kernels_mel_nnls.h"
 #include "plan.h"
 
@@ -17,29 +18,8 @@ namespace {
 
 constexpr int kLdsBytes = 160 * 1024;
 
-struct DevMem {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevMem() {
-    if (p) {
-      (void)hipFree(p);
-      account_bytes(-(int64_t)bytes);
-    }
-  }
-  int alloc(size_t n) {
-    hipError_t e = hipMalloc(&p, n ? n : 16);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return fail(SPECINV_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(e));
-    }
-    bytes = n ? n : 16;
-    account_bytes((int64_t)bytes);
-    return SPECINV_OK;
-  }
-};
-
-int upload(DevMem& d, const void* src, size_t n, hipStream_t stream) {
-  SI_TRY(d.alloc(n));
+int upload(DevBuf& d, const void* src, size_t n, hipStream_t stream) {
+  SI_TRY(d.reserve(n));
   if (n) SI_HIP(hipMemcpyAsync(d.p, src, n, hipMemcpyHostToDevice, stream));
   return SPECINV_OK;
 }
@@ -49,7 +29,7 @@ int upload(DevMem& d, const void* src, size_t n, hipStream_t stream) {
 struct MelNnlsState {
   int n_mels = 0, nseg = 0, nwr = 0, nwc = 0, piece = 0;
   double lipschitz = 0;
-  DevMem wr, wc, seg, rowseg, col, beta;
+  DevBuf wr, wc, seg, rowseg, col, beta;
   int n_beta = 0;
   long long stage_bytes = 0;   // the band form's bytes in LDS
 };
@@ -103,7 +83,7 @@ int ensure_beta(PlanBase& pl, MelNnlsState& st, int n_iter) {
     beta[k] = (t - 1.0) / tn;
     t = tn;
   }
-  DevMem fresh;
+  DevBuf fresh;
   SI_TRY(upload(fresh, beta.data(), beta.size() * sizeof(double), pl.stream));
   SI_HIP(hipStreamSynchronize(pl.stream));
   std::swap(st.beta.p, fresh.p);
