@@ -13,10 +13,12 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
+from . import _lib
 from .plan import StftArgs, get_plan
 
 
@@ -138,6 +140,74 @@ def _cubic_step(xa, fa, ga, xb, fb, gb, bounds=None):
     return min(max(pos, lo), hi)
 
 
+# a point on the search line: step, loss, gradient, g.d and - where the evaluation's read brought them along - max|g|, max|d|
+_Point = namedtuple("_Point", "t f g gtd g_absmax d_absmax", defaults=(None, None))
+
+
+def _strong_wolfe(phi, t, f0, g0, gtd0, max_ls, d_norm=None, c1=1e-4, c2=0.9):
+    """Strong-Wolfe line search (torch.optim.lbfgs._strong_wolfe: bracket, cubic interpolation, zoom) from the point with loss
+    f0, gradient g0 and slope gtd0 = g0.d.  `phi(step)` evaluates a trial point and returns its `_Point`; however it does
+    that, the decisions are the same, in the same order, on the same values.  `d_norm` is max|d|; None: the first trial's
+    read brings it.  Returns (accepted point, evaluations, max|d|); the accepted point may be the starting one (step 0)."""
+    new = phi(t)
+    if d_norm is None:
+        d_norm = new.d_absmax
+    evals, it = 1, 0
+    start = prev = _Point(0.0, f0, g0, gtd0)
+    done, br = False, None
+    while it < max_ls:
+        if new.f > f0 + c1 * new.t * gtd0 or (it > 1 and new.f >= prev.f):
+            br = [prev, new]
+            break
+        if abs(new.gtd) <= -c2 * gtd0:
+            br, done = [new], True
+            break
+        if new.gtd >= 0:
+            br = [prev, new]
+            break
+        nxt = _cubic_step(prev.t, prev.f, prev.gtd, new.t, new.f, new.gtd, (new.t + 0.01 * (new.t - prev.t), new.t * 10))
+        prev = new
+        new = phi(nxt)
+        evals += 1
+        it += 1
+    if it == max_ls:
+        br = [start, new]
+
+    stalled = False
+    lo, hi = (0, 1) if br[0].f <= br[-1].f else (1, 0)
+    while not done and it < max_ls:
+        # torch.optim.LBFGS.step does not forward its tolerance_change to the line search: the bracket test always
+        # uses _strong_wolfe's own default of 1e-9
+        if abs(br[1].t - br[0].t) * d_norm < 1e-9:
+            break
+        t = _cubic_step(br[0].t, br[0].f, br[0].gtd, br[1].t, br[1].f, br[1].gtd)
+        bmax, bmin = max(br[0].t, br[1].t), min(br[0].t, br[1].t)
+        margin = 0.1 * (bmax - bmin)
+        if min(bmax - t, t - bmin) < margin:
+            if stalled or t >= bmax or t <= bmin:
+                t = bmax - margin if abs(t - bmax) < abs(t - bmin) else bmin + margin
+                stalled = False
+            else:
+                stalled = True
+        else:
+            stalled = False
+        new = phi(t)
+        evals += 1
+        it += 1
+        if new.f > f0 + c1 * t * gtd0 or new.f >= br[lo].f:
+            br[hi] = new
+            lo, hi = (0, 1) if br[0].f <= br[1].f else (1, 0)
+        else:
+            if abs(new.gtd) <= -c2 * gtd0:
+                done = True
+            elif new.gtd * (br[hi].t - br[lo].t) >= 0:
+                br[hi] = br[lo]
+            br[lo] = new
+    if len(br) == 1:
+        lo = 0
+    return br[lo], evals, d_norm
+
+
 class LBFGS:
     """Optimises the flat tensor `x` in place.  `step(fg)` performs one `optimizer.step`:
     `fg(x)` must return (loss: float, grad: tensor like x)."""
@@ -167,7 +237,10 @@ class LBFGS:
         self.prev_loss = None
         self._board = None
         self._dev = None                       # device-resident optimiser: None undecided, False not taken, else its handle
+        self._dev_opts = None                  # ... the options it copied at its first step
+        self._dev_poisoned = False             # ... whether a step of it failed half-way
         self._dev_history = 0
+        self.dev_iterations = None             # ... (lean, full, suspensions) of its last step
         self.time_objective = 0                # benchmarks: HIP events around every k-th objective evaluation of the device path
         self.objective_ms, self.objective_timed, self.objective_launches = 0.0, 0, 0
 
@@ -253,84 +326,74 @@ class LBFGS:
             ops.axpy(al[i] - be, self.ss[i], r)
         return r
 
-    def _wolfe(self, fg, x0, t, d, f0, g0, gtd0, max_ls, c1=1e-4, c2=0.9):
-        ops = self.ops
+    # ---- what the step loops below share -----------------------------------------------------------
+    def _push_pair(self, y, s, ys, yy=None):
+        """The curvature-pair update: y = g - g_prev, s = t d enter the memory when y.s > 1e-10 (the oldest pair leaves a
+        full memory) and set the initial Hessian scale y.s / y.y; otherwise the memory stays as it was.  `yy` None: y.y is
+        taken here, for an accepted pair only.  Returns (accepted, an old pair was dropped)."""
+        ok = ys > 1e-10
+        self.pairs_accepted += ok
+        self.pairs_rejected += not ok
+        if not ok:
+            return False, False
+        dropped = len(self.ys) == self.history_size
+        if dropped:
+            self._drop_oldest()
+        self.ys.append(y)
+        self.ss.append(s)
+        self.rho.append(1.0 / ys)
+        yy = yy if yy is not None else self.ops.dot(y, y)
+        self.h_diag = ys / yy
+        self._pushed = (ys, yy)
+        return True, dropped
 
-        def phi(step):
-            trial = x0.clone()
-            ops.axpy(step, d, trial)
-            f, g = fg(trial)
-            return f, g, ops.dot(g, d)
+    def _direction_packed(self, g, pair, t, gd):
+        """The pair update and the new direction of the packed loops, from products already read: `pair` is what
+        `_pair_products` returns, `gd` = g.d of the direction just stepped along.  The products of the new pair with g follow by
+        linearity (s.g = t d.g, y.g = g.g - g_prev.g), and so does g.d of the new direction, a linear combination of vectors
+        whose products with g are all known.  Returns that combination (vectors, coefficients) and its g.d."""
+        y, s, ys, yy, gg, ggp, sg, yg = pair
+        accepted, dropped = self._push_pair(y, s, ys, yy)
+        if accepted:
+            # `sg`, `yg` cover the memory as it stood when they were taken: where that was a full memory, the dropped pair's
+            # products go too.  (`_step_wolfe_packed` takes them right before this update, i.e. after the previous append, so
+            # they always cover the whole memory; `_step_packed` takes them with the evaluation, over the memory of that moment.)
+            if dropped and len(sg) == self.history_size:
+                sg, yg = sg[1:], yg[1:]
+            sg = np.append(sg, t * gd)                     # s_new . g = t (d . g)
+            yg = np.append(yg, gg - ggp)                   # y_new . g = g . g - g_prev . g
+        self._gram_append(sg, yg)
+        coefs = self._gram_coefficients(sg, yg)
+        m = len(self.ss)
+        gtd = coefs[0] * gg + float(np.dot(coefs[1:1 + m], yg)) + float(np.dot(coefs[1 + m:], sg))
+        return [g] + self.ys + self.ss, coefs, gtd
 
-        d_norm = ops.absmax_abssum(d)[0]
-        f_new, g_new, gtd_new = phi(t)
-        evals, it = 1, 0
-        t_prev, f_prev, g_prev, gtd_prev = 0.0, f0, g0, gtd0
-        done, br = False, None
-        while it < max_ls:
-            if f_new > f0 + c1 * t * gtd0 or (it > 1 and f_new >= f_prev):
-                br = [[t_prev, f_prev, g_prev, gtd_prev], [t, f_new, g_new, gtd_new]]
-                break
-            if abs(gtd_new) <= -c2 * gtd0:
-                br, done = [[t, f_new, g_new, gtd_new]], True
-                break
-            if gtd_new >= 0:
-                br = [[t_prev, f_prev, g_prev, gtd_prev], [t, f_new, g_new, gtd_new]]
-                break
-            nxt = _cubic_step(t_prev, f_prev, gtd_prev, t, f_new, gtd_new, (t + 0.01 * (t - t_prev), t * 10))
-            t_prev, f_prev, g_prev, gtd_prev = t, f_new, g_new, gtd_new
-            t = nxt
-            f_new, g_new, gtd_new = phi(t)
-            evals += 1
-            it += 1
-        if it == max_ls:
-            br = [[0.0, f0, g0, gtd0], [t, f_new, g_new, gtd_new]]
+    def _step_length(self, g_abssum):
+        """the step length an iteration starts from: min(1, 1/|g|_1) lr in an optimiser's first iteration, lr afterwards"""
+        return min(1.0, 1.0 / g_abssum) * self.lr if self.total_iters == 1 else self.lr
 
-        stalled = False
-        lo, hi = (0, 1) if br[0][1] <= br[-1][1] else (1, 0)
-        while not done and it < max_ls:
-            # torch.optim.LBFGS.step does not forward its tolerance_change to the line search: the bracket test always
-            # uses _strong_wolfe's own default of 1e-9
-            if abs(br[1][0] - br[0][0]) * d_norm < 1e-9:
-                break
-            t = _cubic_step(br[0][0], br[0][1], br[0][3], br[1][0], br[1][1], br[1][3])
-            bmax, bmin = max(br[0][0], br[1][0]), min(br[0][0], br[1][0])
-            margin = 0.1 * (bmax - bmin)
-            if min(bmax - t, t - bmin) < margin:
-                if stalled or t >= bmax or t <= bmin:
-                    t = bmax - margin if abs(t - bmax) < abs(t - bmin) else bmin + margin
-                    stalled = False
-                else:
-                    stalled = True
-            else:
-                stalled = False
-            f_new, g_new, gtd_new = phi(t)
-            evals += 1
-            it += 1
-            if f_new > f0 + c1 * t * gtd0 or f_new >= br[lo][1]:
-                br[hi] = [t, f_new, g_new, gtd_new]
-                lo, hi = (0, 1) if br[0][1] <= br[1][1] else (1, 0)
-            else:
-                if abs(gtd_new) <= -c2 * gtd0:
-                    done = True
-                elif gtd_new * (br[hi][0] - br[lo][0]) >= 0:
-                    br[hi] = list(br[lo])
-                br[lo] = [t, f_new, g_new, gtd_new]
-        if len(br) == 1:
-            lo = 0
-        return br[lo][1], br[lo][2], br[lo][0], evals
+    def _step_ends(self, n_iter, evals, opt, loss, t, d, d_absmax):
+        """The tests that end a step after an iteration has advanced the iterate.  `d_absmax` None: max|d| is taken here (a
+        launch and a host read), and only once the budget / optimality test has not already ended the step."""
+        if n_iter == self.max_iter or evals >= self.max_eval or opt:
+            return True
+        if d_absmax is None:
+            d_absmax = self.ops.absmax_abssum(d)[0]
+        return abs(t) * d_absmax <= self.tol_change or abs(loss - self.prev_loss) < self.tol_change
+
+    def _get_board(self):
+        if self._board is None or self._board.numel() < 9 + 2 * self.history_size:
+            self._board = self.ops.board(9 + 2 * self.history_size)
+        return self._board
 
     # ---- one optimizer.step, one host synchronisation per inner iteration ------------------------
     def _batch(self, fg, x, d, t):
         """Everything the next decisions need, enqueued back to back and fetched with ONE read: the objective at x (loss,
         gradient g), the step statistics {g.d, sum|g|, max|g|, max|d|} and - once there is a previous gradient - the
         curvature pair y = g - g_prev, s = t d with {y.s, y.y, g.g, g.g_prev} and the products of g with the memory."""
-        ops = self.ops
+        ops, bd = self.ops, self._get_board()
         m = len(self.ss)
         have_prev = self.total_iters >= 1
-        if self._board is None or self._board.numel() < 9 + 2 * self.history_size:
-            self._board = ops.board(9 + 2 * self.history_size)
-        bd = self._board
         g = ops.eval_into(fg, x, bd, 0)
         y = s = None
         if not have_prev:
@@ -344,17 +407,16 @@ class LBFGS:
             if m:
                 ops.multi_dot_into(g, self.ss + self.ys, bd, 9)
         v = ops.read(bd, 9 + 2 * m if have_prev else 5)
-        out = dict(g=g, loss=v[0], gd=v[1], g_abssum=v[2], g_absmax=v[3], d_absmax=v[4], have_prev=have_prev, m=m)
+        out = dict(g=g, loss=v[0], gd=v[1], g_abssum=v[2], g_absmax=v[3], d_absmax=v[4])
         if have_prev:
-            out.update(y=y, s=s, ys=v[5], yy=v[6], gg=v[7], ggp=v[8], sg=np.asarray(v[9:9 + m], dtype=np.float64),
-                       yg=np.asarray(v[9 + m:9 + 2 * m], dtype=np.float64))
+            out["pair"] = (y, s, v[5], v[6], v[7], v[8], np.asarray(v[9:9 + m], dtype=np.float64),
+                           np.asarray(v[9 + m:9 + 2 * m], dtype=np.float64))
         return out
 
     def _step_packed(self, fg):
         """`step` for a backend with device-resident results (no line search): the same decisions in the same order as
-        torch.optim.LBFGS.step, taken from one packed read-back per inner iteration.  The products of the new pair with
-        the gradient follow by linearity (s.g = t d.g, y.g = g.g - g_prev.g), and so does g.d of the new direction, a
-        linear combination of vectors whose products with g are all known."""
+        torch.optim.LBFGS.step, taken from one packed read-back per inner iteration (`_batch`; what the direction needs
+        beyond it follows by linearity, `_direction_packed`)."""
         ops, x = self.ops, self.x
         b = self._batch(fg, x, self.d, self.t)
         loss = first_loss = b["loss"]
@@ -370,32 +432,12 @@ class LBFGS:
             g = b["g"]
             if self.total_iters == 1:
                 self._forget()
-                gtd = -b["gd"]                                 # statistics were taken with d = g: g.g
-                vecs, coefs = None, None
+                vecs, coefs, gtd = None, None, -b["gd"]        # statistics were taken with d = g: g.g
             else:
-                sg, yg = b["sg"], b["yg"]
-                self.pairs_accepted += b["ys"] > 1e-10
-                self.pairs_rejected += not b["ys"] > 1e-10
-                if b["ys"] > 1e-10:
-                    if len(self.ys) == self.history_size:
-                        self._drop_oldest()
-                        if b["m"] == self.history_size:
-                            sg, yg = sg[1:], yg[1:]
-                    self.ys.append(b["y"])
-                    self.ss.append(b["s"])
-                    self.rho.append(1.0 / b["ys"])
-                    self.h_diag = b["ys"] / b["yy"]
-                    self._pushed = (b["ys"], b["yy"])
-                    sg = np.append(sg, t * b["gd"])            # s_new . g = t (d . g)
-                    yg = np.append(yg, b["gg"] - b["ggp"])     # y_new . g = g . g - g_prev . g
-                self._gram_append(sg, yg)
-                coefs = self._gram_coefficients(sg, yg)
-                vecs = [g] + self.ys + self.ss
-                m = len(self.ss)
-                gtd = coefs[0] * b["gg"] + float(np.dot(coefs[1:1 + m], yg)) + float(np.dot(coefs[1 + m:], sg))
+                vecs, coefs, gtd = self._direction_packed(g, b["pair"], t, b["gd"])
             self.prev_grad = g
             self.prev_loss = loss
-            t = min(1.0, 1.0 / b["g_abssum"]) * self.lr if self.total_iters == 1 else self.lr
+            t = self._step_length(b["g_abssum"])
             if gtd > -self.tol_change:
                 d = ops.scaled(-1.0, g) if vecs is None else ops.lincomb(vecs, coefs)
                 break
@@ -404,20 +446,14 @@ class LBFGS:
             else:
                 d = ops.scaled(-1.0, g) if vecs is None else ops.lincomb(vecs, coefs)
                 ops.axpy(t, d, x)
-            ls_evals = 0
             opt = False
             if n_iter != self.max_iter:
                 b = self._batch(fg, x, d, t)
                 loss = b["loss"]
                 opt = b["g_absmax"] <= self.tol_grad
-                ls_evals = 1
-            evals += ls_evals
-            self.func_evals += ls_evals
-            if n_iter == self.max_iter or evals >= self.max_eval or opt:
-                break
-            if abs(t) * b["d_absmax"] <= self.tol_change:
-                break
-            if abs(loss - self.prev_loss) < self.tol_change:
+                evals += 1
+                self.func_evals += 1
+            if self._step_ends(n_iter, evals, opt, loss, t, d, b["d_absmax"]):
                 break
         self.d, self.t = d, t
         return first_loss
@@ -426,10 +462,7 @@ class LBFGS:
     def _eval_point(self, fg, x, d):
         """The objective at x and the statistics a decision needs, enqueued back to back and fetched with ONE read:
         (g, loss, g.d, sum|g|, max|g|, max|d|).  `d` None: the statistics are taken with d = g."""
-        ops = self.ops
-        if self._board is None or self._board.numel() < 9 + 2 * self.history_size:
-            self._board = ops.board(9 + 2 * self.history_size)
-        bd = self._board
+        ops, bd = self.ops, self._get_board()
         if hasattr(fg, "dev_stats") and os.environ.get("SPECINV_LBFGS_FUSED_STATS", "1") != "0":
             g = fg.dev_stats(x, d, bd.data_ptr())          # the statistics ride on the objective's own launches
         else:
@@ -448,83 +481,39 @@ class LBFGS:
         v = ops.read(bd, 9 + 2 * m)
         return y, s, v[5], v[6], v[7], v[8], np.asarray(v[9:9 + m], dtype=np.float64), np.asarray(v[9 + m:9 + 2 * m], dtype=np.float64)
 
-    def _wolfe_packed(self, fg, x0, t, d, f0, g0, gtd0, max_ls, c1=1e-4, c2=0.9):
-        """`_wolfe` (torch.optim.lbfgs._strong_wolfe: bracket, cubic interpolation, zoom) with every trial point evaluated by
-        `_eval_point`: the step, the objective, g.d and max|g| enqueued together, one read-back per trial instead of three.
-        Same decisions in the same order on the same values.  Returns (loss, g, t, evaluations, g.d, max|g|) of the accepted point and max|d|."""
+    def _wolfe(self, fg, x0, t, d, f0, g0, gtd0, max_ls):
+        """`_strong_wolfe` along d from x0, a trial point's scalars read one by one (any objective, any backend)"""
         ops = self.ops
 
+        def phi(step):
+            trial = x0.clone()
+            ops.axpy(step, d, trial)
+            f, g = fg(trial)
+            return _Point(step, f, g, ops.dot(g, d))
+
+        return _strong_wolfe(phi, t, f0, g0, gtd0, max_ls, ops.absmax_abssum(d)[0])
+
+    def _wolfe_packed(self, fg, x0, t, d, f0, g0, gtd0, max_ls):
+        """`_strong_wolfe` along d from x0 with every trial point evaluated by `_eval_point`: one read-back per trial instead of three"""
         trial = torch.empty_like(x0)                       # (the trial point is dropped after its evaluation: one buffer)
 
         def phi(step):
             torch.add(x0, d, alpha=step, out=trial)        # x0 + step d in one launch (a fused multiply-add like `axpy`'s)
             g, f, gd, _, gmax, dmax = self._eval_point(fg, trial, d)
-            return [step, f, g, gd, gmax], dmax
+            return _Point(step, f, g, gd, gmax, dmax)
 
-        new, d_norm = phi(t)
-        evals, it = 1, 0
-        prev = [0.0, f0, g0, gtd0, None]
-        done, br = False, None
-        while it < max_ls:
-            if new[1] > f0 + c1 * new[0] * gtd0 or (it > 1 and new[1] >= prev[1]):
-                br = [prev, new]
-                break
-            if abs(new[3]) <= -c2 * gtd0:
-                br, done = [new], True
-                break
-            if new[3] >= 0:
-                br = [prev, new]
-                break
-            nxt = _cubic_step(prev[0], prev[1], prev[3], new[0], new[1], new[3], (new[0] + 0.01 * (new[0] - prev[0]), new[0] * 10))
-            prev = new
-            new, _ = phi(nxt)
-            evals += 1
-            it += 1
-        if it == max_ls:
-            br = [[0.0, f0, g0, gtd0, None], new]
-        stalled = False
-        lo, hi = (0, 1) if br[0][1] <= br[-1][1] else (1, 0)
-        while not done and it < max_ls:
-            if abs(br[1][0] - br[0][0]) * d_norm < 1e-9:         # (_strong_wolfe's own tolerance_change: torch does not forward its)
-                break
-            t = _cubic_step(br[0][0], br[0][1], br[0][3], br[1][0], br[1][1], br[1][3])
-            bmax, bmin = max(br[0][0], br[1][0]), min(br[0][0], br[1][0])
-            margin = 0.1 * (bmax - bmin)
-            if min(bmax - t, t - bmin) < margin:
-                if stalled or t >= bmax or t <= bmin:
-                    t = bmax - margin if abs(t - bmax) < abs(t - bmin) else bmin + margin
-                    stalled = False
-                else:
-                    stalled = True
-            else:
-                stalled = False
-            new, _ = phi(t)
-            evals += 1
-            it += 1
-            if new[1] > f0 + c1 * t * gtd0 or new[1] >= br[lo][1]:
-                br[hi] = new
-                lo, hi = (0, 1) if br[0][1] <= br[1][1] else (1, 0)
-            else:
-                if abs(new[3]) <= -c2 * gtd0:
-                    done = True
-                elif new[3] * (br[hi][0] - br[lo][0]) >= 0:
-                    br[hi] = list(br[lo])
-                br[lo] = new
-        if len(br) == 1:
-            lo = 0
-        best = br[lo]
-        return best[1], best[2], best[0], evals, best[3], best[4], d_norm
+        return _strong_wolfe(phi, t, f0, g0, gtd0, max_ls)
 
     def _step_wolfe_packed(self, fg):
         """`step` with line_search_fn='strong_wolfe' for an objective that can leave its loss on the device (`fg.dev`): the
         decisions of torch.optim.LBFGS.step in the same order, taken from ONE packed read-back per evaluation (entry point, every
         trial of the line search) and one per curvature pair, where the general path below reads three scalars one by one around
         every evaluation.  The direction is a linear combination of g and the memory with coefficients from the Gram recursion
-        (`_gram_coefficients`); g.d of the new direction follows from the known products, as in `_step_packed`."""
+        (`_direction_packed`, as in `_step_packed`)."""
         ops, x = self.ops, self.x
         # the entry evaluation; its statistics are taken against the direction of the previous step's last iteration (g . d is
         # needed for the curvature pair: s_new . g = t (d . g)) or, before the first iteration, against g itself (g . g)
-        g, loss, gd_old, g_abssum, g_absmax, d_norm = self._eval_point(fg, x, self.d if self.total_iters >= 1 else None)
+        g, loss, gd, g_abssum, g_absmax, d_absmax = self._eval_point(fg, x, self.d if self.total_iters >= 1 else None)
         first_loss = loss
         evals = 1
         self.func_evals += 1
@@ -538,44 +527,23 @@ class LBFGS:
             if self.total_iters == 1:
                 self._forget()
                 d = ops.scaled(-1.0, g)
-                gtd = -gd_old                                  # (the entry statistics were taken with d = g)
+                gtd = -gd                                      # (the entry statistics were taken with d = g)
             else:
-                y, s, ys, yy, gg, ggp, sg, yg = self._pair_products(g, self.prev_grad, d, t)
-                self.pairs_accepted += ys > 1e-10
-                self.pairs_rejected += not ys > 1e-10
-                if ys > 1e-10:
-                    if len(self.ys) == self.history_size:
-                        self._drop_oldest()
-                        sg, yg = sg[1:], yg[1:]
-                    self.ys.append(y)
-                    self.ss.append(s)
-                    self.rho.append(1.0 / ys)
-                    self.h_diag = ys / yy
-                    self._pushed = (ys, yy)
-                    sg = np.append(sg, t * gd_old)             # s_new . g = t (d . g)
-                    yg = np.append(yg, gg - ggp)               # y_new . g = g . g - g_prev . g
-                self._gram_append(sg, yg)
-                coefs = self._gram_coefficients(sg, yg)
-                m = len(self.ss)
-                d = ops.lincomb([g] + self.ys + self.ss, coefs)
-                gtd = coefs[0] * gg + float(np.dot(coefs[1:1 + m], yg)) + float(np.dot(coefs[1 + m:], sg))
+                vecs, coefs, gtd = self._direction_packed(g, self._pair_products(g, self.prev_grad, d, t), t, gd)
+                d = ops.lincomb(vecs, coefs)
             self.prev_grad = g
             self.prev_loss = loss
-            t = min(1.0, 1.0 / g_abssum) * self.lr if self.total_iters == 1 else self.lr
+            t = self._step_length(g_abssum)
             if gtd > -self.tol_change:
                 break
-            loss, g, t, ls_evals, gd_old, ls_gmax, d_norm = self._wolfe_packed(fg, x.clone(), t, d, loss, g, gtd, self.max_eval - evals)
+            p, ls_evals, d_absmax = self._wolfe_packed(fg, x.clone(), t, d, loss, g, gtd, self.max_eval - evals)
+            loss, g, t, gd = p.f, p.g, p.t, p.gtd
             ops.axpy(t, d, x)
-            if ls_gmax is not None:                        # (None: the search ended on its starting point - t = 0, g is the gradient
-                g_absmax = ls_gmax                         # it started from, whose max|g| is known)
-            opt = g_absmax <= self.tol_grad
+            if p.g_absmax is not None:                     # (None: the search ended on its starting point - t = 0, g is the gradient
+                g_absmax = p.g_absmax                      # it started from, whose max|g| is known)
             evals += ls_evals
             self.func_evals += ls_evals
-            if n_iter == self.max_iter or evals >= self.max_eval or opt:
-                break
-            if abs(t) * d_norm <= self.tol_change:
-                break
-            if abs(loss - self.prev_loss) < self.tol_change:
+            if self._step_ends(n_iter, evals, g_absmax <= self.tol_grad, loss, t, d, d_absmax):
                 break
         self.d, self.t = d, t
         return first_loss
@@ -601,7 +569,6 @@ class LBFGS:
         if self.total_iters != 0 or x.dtype != torch.float32 or not x.is_contiguous() or x.data_ptr() % 16 != 0 or \
                 x.numel() != shape[0] * shape[1] or not 1 <= self.history_size <= 120:
             return False
-        from . import _lib
         try:
             handle = plan.lbfgs_dev_create(x.numel(), self.lr, self.max_iter, self.max_eval, self.tol_grad, self.tol_change,
                                            self.history_size, self.time_objective)
@@ -613,7 +580,6 @@ class LBFGS:
         return True
 
     def _step_device(self, fg):
-        from . import _lib
         plan, handle, target, shape = self._dev
         obj = getattr(fg, "device_objective", None)     # the closure of THIS step: same objective kernel, possibly another target
         if obj is None or obj[0] is not plan or tuple(obj[2]) != tuple(shape):
@@ -624,7 +590,7 @@ class LBFGS:
             raise RuntimeError("this optimiser's options were copied to the device at its first step and cannot change afterwards "
                                "(lr, max_iter, max_eval, tolerances, history_size); create a new LBFGS, or run with "
                                "SPECINV_LBFGS_DEVICE=0 to keep the state on the host")
-        if getattr(self, "_dev_poisoned", False):
+        if self._dev_poisoned:
             raise RuntimeError("an earlier step of this optimiser failed after part of it had been enqueued: its device state is "
                                "undefined; create a new LBFGS")
         try:
@@ -649,7 +615,7 @@ class LBFGS:
         return info.first_loss
 
     def __del__(self):
-        dev = getattr(self, "_dev", None)
+        dev = getattr(self, "_dev", None)               # (a constructor that raised on its arguments never set it)
         if dev:
             try:
                 dev[0].lbfgs_dev_destroy(dev[1])
@@ -660,13 +626,12 @@ class LBFGS:
     def step(self, fg):
         if self._device_ok(fg):
             return self._step_device(fg)
-        if self.line_search is None and self.gram and getattr(self.ops, "packed", False) and \
-                os.environ.get("SPECINV_LBFGS_PACKED", "1") != "0":
-            return self._step_packed(fg)
-        if self.line_search is not None and self.gram and getattr(self.ops, "packed", False) and hasattr(fg, "dev") and \
-                os.environ.get("SPECINV_LBFGS_PACKED", "1") != "0":
-            return self._step_wolfe_packed(fg)
         ops, x = self.ops, self.x
+        if self.gram and getattr(ops, "packed", False) and os.environ.get("SPECINV_LBFGS_PACKED", "1") != "0":
+            if self.line_search is None:
+                return self._step_packed(fg)
+            if hasattr(fg, "dev"):
+                return self._step_wolfe_packed(fg)
         fused = hasattr(ops, "pair") and hasattr(ops, "stats")     # one pass per group of vector operations
         loss, g = fg(x)
         first_loss = loss
@@ -691,17 +656,7 @@ class LBFGS:
                     ops.axpy(-1.0, self.prev_grad, y)
                     s = ops.scaled(t, d)
                     ys, yy = ops.dot(y, s), None
-                self.pairs_accepted += ys > 1e-10
-                self.pairs_rejected += not ys > 1e-10
-                if ys > 1e-10:
-                    if len(self.ys) == self.history_size:
-                        self._drop_oldest()
-                    self.ys.append(y)
-                    self.ss.append(s)
-                    self.rho.append(1.0 / ys)
-                    yy = yy if yy is not None else ops.dot(y, y)
-                    self.h_diag = ys / yy
-                    self._pushed = (ys, yy)
+                self._push_pair(y, s, ys, yy)
                 d = self._direction(g)
             self.prev_grad = g if fused else g.clone()     # fg returns a fresh tensor: nothing writes into it later
             self.prev_loss = loss
@@ -710,15 +665,13 @@ class LBFGS:
             else:
                 gtd, d_absmax = ops.dot(g, d), None
                 g_abssum = ops.absmax_abssum(g)[1] if self.total_iters == 1 else None
-            if self.total_iters == 1:
-                t = min(1.0, 1.0 / g_abssum) * self.lr
-            else:
-                t = self.lr
+            t = self._step_length(g_abssum)
             if gtd > -self.tol_change:
                 break
             ls_evals = 0
             if self.line_search is not None:
-                loss, g, t, ls_evals = self._wolfe(fg, x.clone(), t, d, loss, g, gtd, self.max_eval - evals)
+                p, ls_evals, _ = self._wolfe(fg, x.clone(), t, d, loss, g, gtd, self.max_eval - evals)
+                loss, g, t = p.f, p.g, p.t
                 ops.axpy(t, d, x)
                 opt = ops.absmax_abssum(g)[0] <= self.tol_grad
             else:
@@ -730,13 +683,7 @@ class LBFGS:
                     ls_evals = 1
             evals += ls_evals
             self.func_evals += ls_evals
-            if n_iter == self.max_iter or evals >= self.max_eval or opt:
-                break
-            if d_absmax is None:
-                d_absmax = ops.absmax_abssum(d)[0]
-            if abs(t) * d_absmax <= self.tol_change:
-                break
-            if abs(loss - self.prev_loss) < self.tol_change:
+            if self._step_ends(n_iter, evals, opt, loss, t, d, d_absmax):
                 break
         self.d, self.t = d, t
         return first_loss

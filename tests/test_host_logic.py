@@ -256,6 +256,41 @@ def test_lbfgs_control_flow_retraces_torch(tag, kw, backend):
     np.testing.assert_allclose(x.numpy(), g[f"x_{tag}"], rtol=1e-4, atol=1e-6)
 
 
+@pytest.mark.parametrize("tag,kw", [("wolfe", dict(max_iter=40, history_size=5, line_search_fn="strong_wolfe")),
+                                    ("wolfe_h100", dict(max_iter=25, line_search_fn="strong_wolfe"))])
+def test_lbfgs_packed_wolfe_retraces_torch(tag, kw):
+    """The strong-Wolfe loop with one synchronisation per evaluation (`_step_wolfe_packed`, the route a device objective takes)
+    on CPU tensors, against what torch.optim.LBFGS gave (the g9 fixture): same losses, same iterate, and one read per objective
+    evaluation plus one per curvature pair - every inner iteration but the optimiser's first takes one."""
+    g = load_golden("g9_lbfgs_rosen")
+    x = torch.from_numpy(g["x0"].copy())
+    losses = []
+
+    def fg(v):
+        a, b = v[1:] - v[:-1] ** 2, 1.0 - v[:-1]
+        f = float((100.0 * a * a + b * b).sum())
+        gr = torch.zeros_like(v)
+        gr[1:] += 200.0 * a
+        gr[:-1] += -400.0 * a * v[:-1] - 2.0 * b
+        losses.append(f)
+        return f, gr
+
+    fg.dev = None                  # `step` routes on the attribute alone: PackedTorchVecOps.eval_into calls fg itself
+    ops = PackedTorchVecOps()
+    opt = LBFGS(x, vec_ops=ops, **kw)
+    taken = []
+    orig = opt._step_wolfe_packed
+    opt._step_wolfe_packed = lambda f: (taken.append(1), orig(f))[1]
+    for _ in range(2):
+        opt.step(fg)
+    assert len(taken) == 2
+    ref = g[f"losses_{tag}"]
+    assert len(losses) == len(ref) == opt.func_evals
+    np.testing.assert_allclose(losses, ref, rtol=5e-4, atol=1e-7)
+    np.testing.assert_allclose(x.numpy(), g[f"x_{tag}"], rtol=1e-4, atol=1e-6)
+    assert ops.reads == opt.func_evals + (opt.total_iters - 1)
+
+
 def test_lbfgs_option_validation():
     x = torch.zeros(3)
     with pytest.raises(ValueError):
