@@ -1,6 +1,6 @@
 // L-BFGS with the decisions on the device: one `optimizer.step` (reference: torch_specinv/methods.py:553 ->
 // torch.optim.LBFGS.step, third-party; no line search - strong Wolfe runs on the host-driven packed loop, lbfgs.py) is ENQUEUED as a
-// whole and the host synchronises once per step instead of once per inner iteration (kernels_lbfgs.h / lbfgs.py:_step_packed:
+// whole and the host synchronises once per step instead of once per inner iteration (kernels_vec.h / lbfgs.py:_step_packed:
 // ~0.05 ms of host turnaround around a 0.15 ms objective).
 //
 // An inner iteration is TWO launches while the memory is empty and the frame walk (kernels_objective_walk.h) serves the objective:
@@ -31,7 +31,9 @@
 #include <memory>
 #include <vector>
 
-#include "kernels_lbfgs.h"
+#include "dev_buf.h"
+#include "lbfgs_state.h"
+#include "objective_host.h"
 
 namespace specinv {
 
@@ -799,6 +801,44 @@ int lbd_grow(P& pl, LbfgsDev<float>& L, int iterations_ahead) {
   return SPECINV_OK;
 }
 
+// the iterate back in the caller's buffer after deferred steps, and the record told so (the caller checks the launches)
+template <typename P>
+void lbd_settle(P& pl, LbfgsDev<float>& L) {
+  hipLaunchKernelGGL((k_lbd_settle_x<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), L.n);
+  hipLaunchKernelGGL(k_lbd_settled, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
+}
+
+// an implicit direction (LbdState::d_implicit: d = c0 g_prev, stored nowhere) written out for the full form, which reads it.  The
+// flag is cleared in the record on the device, or - on_host - in the host's mirror, which the caller is about to upload.
+template <typename P>
+int lbd_materialise_d(P& pl, LbfgsDev<float>& L, bool on_host) {
+  hipLaunchKernelGGL((k_lbd_materialise_d<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), L.n);
+  if (on_host) L.h.d_implicit = 0;
+  else hipLaunchKernelGGL(k_lbd_clear_implicit, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
+  SI_HIP(hipGetLastError());
+  return SPECINV_OK;
+}
+
+// what a finished step reports, from the record read back (objective_timed / objective_ms: lbd_step_run adds the events' times)
+inline void lbd_fill_info(const LbfgsDev<float>& L, specinv_lbfgs_info* info) {
+  info->first_loss = L.h.first_loss;
+  info->loss = L.h.loss;
+  info->t = L.h.t;
+  info->total_iters = L.h.total_iters;
+  info->func_evals = L.h.func_evals;
+  info->n_iter = L.h.n_iter;
+  info->history_len = L.h.m;
+  info->pairs_accepted = L.h.pairs_accepted;
+  info->pairs_rejected = L.h.pairs_rejected;
+  info->objective_launches = L.h.evals;
+  info->objective_timed = 0;
+  info->objective_ms = 0.0;
+  info->lean_iterations = L.lean_launches;
+  info->full_iterations = L.full_launches;
+  info->suspensions = L.suspensions;
+  info->reserved_ = 0;
+}
+
 // one optimizer.step: everything enqueued, one synchronisation at the end (one more if a lean chain is suspended)
 template <typename P>
 int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* target, specinv_lbfgs_info* info);
@@ -814,8 +854,7 @@ int lbd_step(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* targ
   if (rc != SPECINV_OK && L.defer_live) {
     const std::string why = last_error();            // (the settle's own HIP calls must not replace the message)
     (void)hipGetLastError();
-    hipLaunchKernelGGL((k_lbd_settle_x<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), L.n);
-    hipLaunchKernelGGL(k_lbd_settled, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
+    lbd_settle(pl, L);
     (void)hipStreamSynchronize(pl.stream);
     (void)hipGetLastError();
     last_error() = why;
@@ -825,11 +864,20 @@ int lbd_step(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* targ
   return rc;
 }
 
+// the form of an inner iteration (the table at the top of this file), picked at the start of a step; a suspended chain resumes in
+// the full form
+enum class LbdForm {
+  full,    // pairs in the memory: k_lbd_multi_dot, k_lbd_decide, k_lbd_lincomb_step (+ the objective's two launches)
+  lean3,   // empty memory: objective, epilogue, k_lbd_direction_lean
+  lean2    // ... and the step deferred into the frame walk: objective and epilogue, which takes the decisions
+};
+
 template <typename P>
 int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* target, specinv_lbfgs_info* info) {
   SI_CHECK(x && target && info, SPECINV_EINVAL, "null pointer");
   SI_CHECK((int64_t)pl.B() * len == L.n, SPECINV_EINVAL, "signal size does not match the optimiser's parameter vector");
   SI_CHECK(((uintptr_t)x & 15) == 0, SPECINV_EINVAL, "x is not 16-byte aligned");
+  const ObjKnobs kn = ObjKnobs::read();
   SI_TRY(lbd_grow(pl, L, L.h.max_iter));
   const int64_t n = L.n;
   const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ceil_div(n, 256 * 8)));
@@ -838,19 +886,15 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
   L.board_host[0] = 1.0;
   hipLaunchKernelGGL(k_lbd_begin, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
   SI_HIP(hipGetLastError());
+  const ObjRoute rt = obj_route(pl, len, kn);         // the kernel of every evaluation of this step
   // the deferred step: only where the frame walk serves the objective (it is the kernel that applies the step)
-  bool defer = tf_walk_serves(pl, len) && ((uintptr_t)x & 7) == 0;
-  if (const char* e = getenv("SPECINV_LBFGS_DEFER")) {
-    if (e[0] == '0') defer = false;                 // (tests / A-B runs)
-  }
+  const bool defer = rt.kind == kObjWalk && ((uintptr_t)x & 7) == 0 && kn.defer;
   L.x_user = x;
   L.defer_live = defer;
   // evaluate() launches that EXECUTED, as index ranges [lo, hi): after a suspended lean chain the no-op launches of its tail sit
   // between the chain's executed evaluations and the resumed ones (only executed launches are summed into objective_ms)
   std::vector<std::pair<int, int>> exec_ranges;
   int exec_lo = 0, exec_counted = 0;
-  int tail_fence = 1;                               // the epilogue's rows handed over by release / acquire (0: round 5's write-through protocol)
-  if (const char* e = getenv("SPECINV_LBFGS_TAIL_FENCE")) tail_fence = e[0] != '0';
   int n_eval_launched = 0;
   // objective + epilogue on the record that is current NOW; k_decide > 0: the epilogue also takes iteration k_decide's decisions
   // (the two-launch lean iteration) and writes the OTHER record
@@ -874,7 +918,6 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
     sr.d_implicit = &st->d_implicit;
     sr.c0_d = &st->c0_d;
     sr.rows = L.rows.template as<double>();
-    bool used = false;
     const bool timed = L.time_objective > 0 && n_eval_launched % L.time_objective == 0 && (size_t)(2 * n_eval_launched + 1) < L.ev.size();
     if (timed) SI_HIP(hipEventRecord(L.ev[2 * n_eval_launched], pl.stream));
     fast::ObjDecide dec{};
@@ -885,10 +928,9 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
       dec.board = L.board_dev;
       dec.rows = sr.rows;
       dec.k = k_decide;
-      dec.fence = tail_fence;
+      dec.fence = kn.tail_fence ? 1 : 0;     // the epilogue's rows handed over by release / acquire (0: round 5's write-through protocol)
     }
-    SI_TRY(tf_loss_grad_fused(pl, x, len, target, nullptr, L.g0, &used, nullptr, &ctl, &sr, k_decide > 0 ? &dec : nullptr));
-    SI_CHECK(used, SPECINV_EUNSUPPORTED, "the one-launch objective does not cover this configuration");
+    SI_TRY(tf_loss_grad_fused(pl, rt, x, len, target, nullptr, L.g0, nullptr, &ctl, &sr, k_decide > 0 ? &dec : nullptr));
     if (timed) SI_HIP(hipEventRecord(L.ev[2 * n_eval_launched + 1], pl.stream));
     ++n_eval_launched;
     return SPECINV_OK;
@@ -898,34 +940,26 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
   const int64_t pieces = n / 4 + 1;
   const int lean_grid = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ceil_div(pieces, 256 * kLbdLeanItems)));
   const double* rows = L.rows.template as<double>();
-  bool lean = L.h.m == 0;                           // the memory as the host last saw it (a fresh optimiser: empty)
-  if (const char* e = getenv("SPECINV_LBFGS_LEAN")) {
-    if (e[0] == '0') lean = false;                  // (tests / A-B runs: the full form from the first iteration)
-  }
-  if (!lean && L.h.d_implicit) {                    // (only when the form is forced: a lean chain clears the flag before it hands over)
-    hipLaunchKernelGGL((k_lbd_materialise_d<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), n);
-    hipLaunchKernelGGL(k_lbd_clear_implicit, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
-    SI_HIP(hipGetLastError());
-  }
-  // the lean iteration in two launches: with the step deferred into the frame walk nothing is left to stream unless a pair is
-  // accepted, and that iteration hands over to the full form - the decisions ride in the epilogue (lbd_tail_decide)
-  bool lean2 = lean && defer;
-  if (const char* e = getenv("SPECINV_LBFGS_LEAN2")) {
-    if (e[0] == '0') lean2 = false;
-  }
-  if (!lean2) SI_TRY(evaluate(0));                  // (the entry evaluation; lean2: iteration 1's evaluation carries its decision)
+  // lean while the memory is empty, as the host last saw it (a fresh optimiser: empty).  In two launches with the step deferred into
+  // the frame walk: nothing is left to stream unless a pair is accepted, and that iteration hands over to the full form - the
+  // decisions ride in the epilogue (lbd_tail_decide)
+  LbdForm form = LbdForm::full;
+  if (L.h.m == 0 && kn.lean) form = defer && kn.lean2 ? LbdForm::lean2 : LbdForm::lean3;
+  // (only when the full form is forced: a lean chain clears the flag before it hands over)
+  if (form == LbdForm::full && L.h.d_implicit) SI_TRY(lbd_materialise_d(pl, L, false));
+  if (form != LbdForm::lean2) SI_TRY(evaluate(0));    // (the entry evaluation; lean2: iteration 1's evaluation carries its decision)
   int k = 1, k_first = 1;
   for (;;) {
     for (; k <= L.h.max_iter; ++k) {
       if (k > k_first && L.board_host[0] == 0.0) break;   // a peek at what the device has decided so far (may lag: only saves no-ops)
       LbdPtrs<float> p = L.ptrs();
-      if (lean && lean2) {
+      if (form == LbdForm::lean2) {
         SI_TRY(evaluate(k));
         L.par ^= 1;
         ++L.lean_launches;
         continue;
       }
-      if (lean) {
+      if (form == LbdForm::lean3) {
         hipLaunchKernelGGL((k_lbd_direction_lean<float>), dim3(lean_grid), dim3(256), 0, pl.stream, p, k, n, rows, scale,
                            defer ? 1 : 0);
         L.par ^= 1;
@@ -942,8 +976,7 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
     }
     // a step cut short by the peek leaves `active` set on the device only if the device had not stopped: it had (the peek read 0)
     if (defer) {                                    // the iterate back in the caller's buffer (a suspended chain: its last one)
-      hipLaunchKernelGGL((k_lbd_settle_x<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), n);
-      hipLaunchKernelGGL(k_lbd_settled, dim3(1), dim3(1), 0, pl.stream, L.state(L.par));
+      lbd_settle(pl, L);
       SI_HIP(hipGetLastError());
     }
     SI_HIP(hipMemcpyAsync(&L.h, L.state(L.par), sizeof(LbdState), hipMemcpyDeviceToHost, pl.stream));
@@ -955,12 +988,9 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
     exec_ranges.emplace_back(exec_lo, std::min(n_eval_launched, exec_lo + (L.h.evals - exec_counted) + 1));   // (+ the suspended iteration's own)
     exec_counted = L.h.evals + 1;
     exec_lo = n_eval_launched;
-    lean = false;
-    if (L.h.d_implicit) {                           // (a two-launch chain hands over at the iteration that accepts its first pair:
-      hipLaunchKernelGGL((k_lbd_materialise_d<float>), dim3(1024), dim3(256), 0, pl.stream, L.ptrs(), n);   // s = t d is read from d)
-      L.h.d_implicit = 0;
-      SI_HIP(hipGetLastError());
-    }
+    form = LbdForm::full;
+    // (a two-launch chain hands over at the iteration that accepts its first pair: s = t d is read from d)
+    if (L.h.d_implicit) SI_TRY(lbd_materialise_d(pl, L, true));
     k = k_first = L.h.resume_k;
     L.h.suspended = 0;
     L.h.active = 1;
@@ -969,22 +999,7 @@ int lbd_step_run(P& pl, LbfgsDev<float>& L, float* x, int64_t len, const float* 
     L.board_host[0] = 1.0;
   }
   L.accepted_seen = L.h.pairs_accepted;
-  info->first_loss = L.h.first_loss;
-  info->loss = L.h.loss;
-  info->t = L.h.t;
-  info->total_iters = L.h.total_iters;
-  info->func_evals = L.h.func_evals;
-  info->n_iter = L.h.n_iter;
-  info->history_len = L.h.m;
-  info->pairs_accepted = L.h.pairs_accepted;
-  info->pairs_rejected = L.h.pairs_rejected;
-  info->objective_launches = L.h.evals;
-  info->objective_timed = 0;
-  info->objective_ms = 0.0;
-  info->lean_iterations = L.lean_launches;
-  info->full_iterations = L.full_launches;
-  info->suspensions = L.suspensions;
-  info->reserved_ = 0;
+  lbd_fill_info(L, info);
   if (L.time_objective) {
     exec_ranges.emplace_back(exec_lo, std::min(n_eval_launched, exec_lo + std::max(0, L.h.evals - exec_counted)));
     for (const auto& r : exec_ranges)                 // (executed ones; gated launches are no-ops)

@@ -1,5 +1,5 @@
 // The device-resident optimiser's state record and the scalar decisions of its LEAN iteration (lbfgs_dev.h has the kernels and the
-// host side): what the objective's epilogue (kernels_lbfgs.h) needs to take an iteration's decisions itself, in the workgroup that
+// host side): what the objective's epilogue (kernels_objective_epilogue.h) needs to take an iteration's decisions itself, in the workgroup that
 // finishes last - reference: torch.optim.LBFGS.step (third-party; called from torch_specinv/methods.py:553).
 #pragma once
 #include "common.h"

@@ -13,7 +13,8 @@
 #include "fast_state.h"
 #include "kernels_generic.h"
 #include "wave_api.h"
-#include "kernels_lbfgs.h"
+#include "kernels_vec.h"
+#include "objective_host.h"
 #include "kernels_big.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"

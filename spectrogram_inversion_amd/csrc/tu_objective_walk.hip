@@ -1,5 +1,5 @@
 // k_objective_walk: the log-mel objective as a frame walk (kernels_objective_walk.h), hop = n_fft / 4.  Explicit instantiations: the
-// host side (kernels_lbfgs.h) takes the kernels' addresses from the declaration in objective_args.h.
+// host side (objective_host.h) takes the kernels' addresses from the declaration in objective_args.h.
 #include "kernels_objective_walk.h"
 
 namespace specinv {

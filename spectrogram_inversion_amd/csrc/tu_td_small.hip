@@ -1,5 +1,5 @@
 // k_fused_td<R, OV>: the signal-form Griffin-Lim kernel at the other overlaps, n_fft 512 / 1024.
-// Explicit instantiations: the host side (fast_state.h / rtisi_fast_host.h / kernels_lbfgs.h) takes these kernels' addresses from
+// Explicit instantiations: the host side (fast_state.h / rtisi_fast_host.h / objective_host.h) takes these kernels' addresses from
 // the declarations in fast_core.h / rtisi_fast_host.h / objective_args.h; a kernel missing here is an undefined symbol at link time.
 #include "kernels_fast_td.h"
 

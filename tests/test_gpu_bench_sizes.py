@@ -302,7 +302,7 @@ def test_c5_optimiser_step_full_size(monkeypatch):
     iterations of torch.optim.LBFGS, every pair rejected by the curvature guard (methods.py:543-556) - on the path the C5 number is
     timed on: the frame walk at 2048 waves applying the deferred step, the epilogue's 256 workgroups handing their rows to whichever
     finishes last (an acquire-release ticket since round 6).  Against its three-launch forms and round 5's hand-over (write-through
-    stores retired before a relaxed ticket, kernels_lbfgs.h): iterates bit for bit, same counters; against the host-driven loop: same counters, iterates to the
+    stores retired before a relaxed ticket, kernels_objective_epilogue.h): iterates bit for bit, same counters; against the host-driven loop: same counters, iterates to the
     order of the float64 sums.  The two-launch form then twenty more times in this process: the ticket protocol has 256 workgroups
     over 8 XCDs to go wrong on, and every run must land on the same bits."""
     tr, target, x0, _ = _c5_inputs()
