@@ -166,7 +166,21 @@ int specinv_admm_run(specinv_plan* plan, int max_iter, int eva_iter, double tol,
                      specinv_eval* evals_out, int* n_evals_out, int* iters_done_out,
                      specinv_eval_cb cb, void* user);
 
-/* current waveform estimate status_dict['x'] (B, L) of the running GLA / ADMM state */
+/* ---- MISI (Gunawan & Sen 2010: multiple input spectrogram inversion) -------------------- */
+/* MISI: Griffin-Lim without momentum on batch = n_mix * n_src items (item b*n_src + k is source k of mixture b), coupled after
+ * every inverse transform by x_k += (mix_b - sum_k x_k) / n_src.  init_spec / mag as specinv_gla_init (init_spec required:
+ * the host layer forms the mixture-phase start); mixture (n_mix, mix_stride) device array of the plan's dtype, the first
+ * specinv_plan_length samples of each row are used (the plan keeps a copy).  SPECINV_EINVAL, before anything is enqueued: NULL
+ * init_spec or mixture, n_src < 1, a batch that is no multiple of n_src, mix_stride below the plan's length. */
+int specinv_misi_init(specinv_plan* plan, const void* init_spec, const void* mag, const void* mixture, int64_t mix_stride, int n_src);
+/* n_iter times: one projection launch, one coupling launch.  An evaluating iteration's sums are the projection's: |STFT| of the
+ * mixed signals that entered it against the target.  SPECINV_ESTATE before specinv_misi_init; specinv_gla_iterate / _run and
+ * specinv_admm_iterate / _run return SPECINV_ESTATE on a plan in the MISI state (they would drop the coupling step). */
+int specinv_misi_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]);
+int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
+                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user);
+
+/* current waveform estimate status_dict['x'] (B, L) of the running GLA / ADMM / MISI state */
 int specinv_get_wave(specinv_plan* plan, void* x_out);
 /* running state as (B, F, T) complex: which = 0 pre_spec (GLA) or X (ADMM), 1 U (ADMM), 2 Y = X + U (ADMM, always
  * available; X and U need specinv_plan_keep_state) - for state-parity tests */

@@ -16,7 +16,11 @@ struct FastState {
   bool xform_ok = false;
   bool two = false;
   bool keep_state = false;
+  bool plain_state = false;
   int n_partials = 0;
+  int nchunks = 0, skew = 0, OV = 0;
+  T* state_rows() const { return nullptr; }
+  const T* state_tails() const { return nullptr; }
   int setup(const specinv_stft_cfg&, const std::vector<T>&, int64_t, int) { return SPECINV_OK; }
   void geometry(int out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
   template <typename P>
@@ -163,6 +167,12 @@ struct FastState<float> {
   // (specinv_plan_keep_state), by the last iteration of every iterate() call.
   bool keep_state = false, xu_valid = false;
   DevBuf Xb, Xmid, Ub, Umid;
+  // A method that edits the signal between two launches (MISI's coupling step, kernels_misi.h) runs Griffin-Lim on the kernels
+  // that keep it as xb[cur] (+ xtail[cur] on the fused kernels), never in the signal form below - the routing keep_state selects.
+  // state_rows(): the rows the next launch reads; state_tails(): the chunk tails it adds on load (nullptr: the rows are whole)
+  bool plain_state = false;
+  float* state_rows() const { return xb[cur].template as<float>(); }
+  const float* state_tails() const { return (!semi && nchunks > 1) ? xtail[cur].template as<float>() : nullptr; }
   // Griffin-Lim on k_fused4_td: the momentum state is the signal z (zb), Pb keeps the starting spectrum c0
   bool td = false;
   int td_t = 0;          // closure calls so far (z_1 = x_1: the first call reads x itself)
@@ -338,7 +348,7 @@ struct FastState<float> {
     mode = md;
     // (n_fft 4096 runs one wave per SIMD: its vector latency, not the state traffic, is what bounds it there - the signal form
     // measured 0.360 against 0.340 ms per iteration and is not used)
-    td = md == fast::MODE_GLA && (!semi || hopk) && !knobs.fused_template && !keep_state && RR <= 16 && !two;
+    td = md == fast::MODE_GLA && (!semi || hopk) && !knobs.fused_template && !keep_state && !plain_state && RR <= 16 && !two;
     // (the signal-form kernels leave the real-FFT split unscaled, which is exact only for a power-of-two fwd_scale / 2)
     if (pl.cfg.normalized && !hopk) td = false;
     // k_hop_td writes two signals and re-reads z_t where k_hop writes one: at large hops its emission loop overtakes the saved state

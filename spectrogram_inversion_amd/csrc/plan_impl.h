@@ -16,6 +16,7 @@
 #include "kernels_vec.h"
 #include "objective_host.h"
 #include "kernels_big.h"
+#include "kernels_misi.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
 #include "plan.h"
@@ -94,6 +95,8 @@ struct PlanT final : PlanBase {
   int dr_threads = 0;
   double sum_m2 = 0, count = 0;
   T coef = 0;  // lr (GLA) or rho (ADMM)
+  DevBuf misi_mix;                      // MISI: the mixtures, (batch / misi_k, length)
+  int misi_k = 0;                       // ... and the sources per mixture
   FastState<T> fast;
   int tf_kind = -1, tf_mels = 0;
 
@@ -594,7 +597,8 @@ struct PlanT final : PlanBase {
   // ------------------------------------------------------------------------------------
   // shared part of gla_init / admm_init: target + starting spectrum into internal layout,
   // x = ISTFT(start) (methods.py:233 / :453)
-  int init_common(const void* init_spec, const void* magp, int fast_mode) {
+  // (plain_state: FastState::plain_state - the float32 kernels that keep the signal where a kernel between two launches can edit it)
+  int init_common(const void* init_spec, const void* magp, int fast_mode, bool plain_state = false) {
     SI_CHECK(init_spec || magp, SPECINV_EINVAL, "need init_spec and/or mag");
     // torch.stft refuses reflect padding that is not smaller than the signal (methods.py:241 would raise)
     SI_CHECK(!(cfg.center && cfg.pad_mode == SPECINV_PAD_REFLECT && pad >= length), SPECINV_EINVAL,
@@ -604,6 +608,7 @@ struct PlanT final : PlanBase {
     const C* start_user = static_cast<const C*>(init_spec);
     keep_latched = keep_state;
     fast.keep_state = keep_state;
+    fast.plain_state = plain_state;
     if constexpr (std::is_same<T, float>::value) {
       // fused kernels, magnitude input: phase_init writes the pair layout itself (methods.py:106 without the (B, F, T)
       // complex round trip and the two layout passes)
@@ -666,10 +671,59 @@ struct PlanT final : PlanBase {
     return SPECINV_OK;
   }
 
+  // MISI (Gunawan & Sen 2010; the unfolded layer of Wang, Le Roux & Hershey 2018): Griffin-Lim without momentum on batch =
+  // n_mix * n_src items, item b * n_src + k source k of mixture b, every inverse transform followed by the coupling step
+  // x_k += (mix_b - sum_k x_k) / n_src on the signal the next launch reads (launch_mix)
+  int misi_init(const void* init_spec, const void* magp, const void* mixture, int64_t mix_stride, int n_src) override {
+    SI_CHECK(init_spec && mixture, SPECINV_EINVAL, "misi_init needs init_spec (the host layer forms the mixture-phase start) and mixture");
+    SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+    SI_CHECK(B() % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)", B(), n_src);
+    SI_CHECK(mix_stride >= length, SPECINV_EINVAL, "mix_stride (%lld) is smaller than the plan's signal length (%lld)",
+             (long long)mix_stride, (long long)length);
+    method = Method::None;
+    coef = T(0);
+    const int n_mix = B() / n_src;
+    SI_TRY(init_common(init_spec, magp, fast::MODE_GLA, true));
+    SI_TRY(misi_mix.reserve((size_t)n_mix * length * sizeof(T)));
+    SI_HIP(hipMemcpy2DAsync(misi_mix.p, length * sizeof(T), mixture, mix_stride * sizeof(T), length * sizeof(T), n_mix,
+                            hipMemcpyDeviceToDevice, stream));
+    misi_k = n_src;
+    method = Method::Misi;
+    return launch_mix();
+  }
+
+  // The coupling step on the state the next projection launch reads: the plan's x on the coverage kernels (after the overlap-add,
+  // after the swap of the register / ring form); xb[cur] on the float32 wave-level kernels, whose fused forms keep the chunk
+  // tails beside it - the sum takes them in, the correction goes to xb[cur], and xb + tail is again what the launch loads.
+  int launch_mix() {
+    MisiMixArgs<T> a{};
+    a.x = x.as<T>();
+    if (fast_path()) {
+      a.x = fast.state_rows();
+      a.tail = fast.state_tails();
+      if (a.tail != nullptr) {
+        a.n_frames = Tn();
+        a.nchunks = fast.nchunks;
+        a.skew = fast.skew;
+        a.hop = cfg.hop_length;
+        a.nb = fast.OV - 1;
+        a.pb = fast.OV / 2;
+      }
+    }
+    a.mix = misi_mix.as<T>();
+    a.L = length;
+    a.K = misi_k;
+    return misi_mix_launch<T>(a, B() / misi_k, stream);
+  }
+
   int iterate(int n_iter, bool eval_last, double s[4]) override {
     SI_CHECK(method != Method::None, SPECINV_ESTATE, "iterate called before gla_init/admm_init");
     SI_CHECK(n_iter >= 0, SPECINV_EINVAL, "n_iter < 0");
     if (n_iter == 0) return SPECINV_OK;
+    if (method == Method::Misi && n_iter > 1) {          // one projection launch, one mix launch per iteration
+      for (int i = 0; i < n_iter; ++i) SI_TRY(iterate(1, eval_last && i == n_iter - 1, s));
+      return SPECINV_OK;
+    }
     if (fast_path()) {
       fast.keep_state = fast.two ? keep_latched : keep_state;
       SI_TRY(fast.iterate(*this, n_iter, eval_last));
@@ -683,7 +737,7 @@ struct PlanT final : PlanBase {
           const BigCfg<T> bc = big_cfg(length);
           SI_TRY(big_forward(bc, x.as<T>()));
           const dim3 ug((unsigned)ceil_div(N() / 2 + 1, 256), Tn(), B());
-          const int mode = method == Method::Gla ? 0 : 1;
+          const int mode = method == Method::Admm ? 1 : 0;
           C* sb = mode == 0 ? (C*)nullptr : specB.as<C>();
           if (ev) SI_TRY(partials.reserve((size_t)2 * ug.x * ug.y * ug.z * sizeof(double)));
           if (mode == 0) {
@@ -703,12 +757,12 @@ struct PlanT final : PlanBase {
           wa.c = fci;
           wa.x = x.as<T>();
           wa.S0 = specA.as<C>();
-          wa.S1 = method == Method::Gla ? (C*)nullptr : specB.as<C>();
+          wa.S1 = method == Method::Admm ? specB.as<C>() : (C*)nullptr;
           wa.mag = mag.as<T>();
           wa.coef = coef;
           wa.inv1p = inv1p;
           wa.batch = B();
-          wa.mode = method == Method::Gla ? 0 : 1;
+          wa.mode = method == Method::Admm ? 1 : 0;
           wa.eval = ev ? 1 : 0;
           // hop = n_fft / 2, / 4, / 8: the overlap-add in the kernel's registers - no frames buffer, the new signal written to the
           // plan's other signal buffer (the frames of an iteration read the old one), the chunk boundaries finished by k_wave_seams
@@ -744,7 +798,7 @@ struct PlanT final : PlanBase {
         const dim3 grid((Tn() + 1) / 2, B()), blk(use_dr ? dr_threads : frame_threads());   // two frames per complex FFT
         {
           const void* fn = nullptr;
-          const int mode = method == Method::Gla ? 0 : 1;
+          const int mode = method == Method::Admm ? 1 : 0;
           if (use_dr) fn = mode == 0 ? (ev ? (const void*)k_iter_pair_dr<T, 0, true> : (const void*)k_iter_pair_dr<T, 0, false>)
                                      : (ev ? (const void*)k_iter_pair_dr<T, 1, true> : (const void*)k_iter_pair_dr<T, 1, false>);
           else if (use_inplace && blk.x <= 256)
@@ -770,6 +824,8 @@ struct PlanT final : PlanBase {
         SI_TRY(launch_ola(frames.as<T>(), x.as<T>(), true));
       }
     }
+    // (an evaluating iteration's sums are the projection launch's: they describe the mixed signal that entered it)
+    if (method == Method::Misi) SI_TRY(launch_mix());
     if (eval_last) {
       const int64_t n_part = fast_path() ? (int64_t)fast.n_partials
                              : big ? (int64_t)B() * Tn() * ceil_div(N() / 2 + 1, 256)

@@ -214,6 +214,11 @@ int specinv_plan_force_generic(specinv_plan* plan, int on) {
   return SPECINV_OK;
 }
 
+// a plan in the MISI state must not be stepped by another method's entry point: the coupling step would silently be dropped
+#define NOT_MISI(plan, name)                                                                                           \
+  SI_CHECK((plan)->impl->method != Method::Misi, SPECINV_ESTATE,                                                      \
+           name " on a plan in the MISI state would drop the coupling step: use specinv_misi_iterate / specinv_misi_run")
+
 #define ENTER(plan)                                 \
   PLAN_OR_FAIL(plan);                               \
   DeviceGuard guard_;                               \
@@ -247,12 +252,14 @@ int specinv_gla_init(specinv_plan* plan, const void* init_spec, const void* mag,
 }
 int specinv_gla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   ENTER(plan);
+  NOT_MISI(plan, "specinv_gla_iterate");
   SI_CHECK(plan->impl->method == Method::Gla, SPECINV_ESTATE, "specinv_gla_init has not been called");
   return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
 }
 int specinv_gla_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
   ENTER(plan);
+  NOT_MISI(plan, "specinv_gla_run");
   SI_CHECK(plan->impl->method == Method::Gla, SPECINV_ESTATE, "specinv_gla_init has not been called");
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }
@@ -263,13 +270,42 @@ int specinv_admm_init(specinv_plan* plan, const void* init_spec, const void* mag
 }
 int specinv_admm_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   ENTER(plan);
+  NOT_MISI(plan, "specinv_admm_iterate");
   SI_CHECK(plan->impl->method == Method::Admm, SPECINV_ESTATE, "specinv_admm_init has not been called");
   return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
 }
 int specinv_admm_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
                      int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
   ENTER(plan);
+  NOT_MISI(plan, "specinv_admm_run");
   SI_CHECK(plan->impl->method == Method::Admm, SPECINV_ESTATE, "specinv_admm_init has not been called");
+  return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
+}
+
+int specinv_misi_init(specinv_plan* plan, const void* init_spec, const void* mag, const void* mixture, int64_t mix_stride, int n_src) {
+  // (the argument errors before the device is touched; PlanT::misi_init repeats them for its own callers)
+  SI_CHECK(init_spec && mixture, SPECINV_EINVAL, "specinv_misi_init: NULL %s (init_spec is required: the host layer forms the mixture-phase start)",
+           init_spec ? "mixture" : "init_spec");
+  SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->cfg.batch % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)",
+           plan->impl->cfg.batch, n_src);
+  SI_CHECK(mix_stride >= plan->impl->length, SPECINV_EINVAL, "mix_stride (%lld) is smaller than the plan's signal length (%lld)",
+           (long long)mix_stride, (long long)plan->impl->length);
+  ENTER(plan);
+  return plan->impl->misi_init(init_spec, mag, mixture, mix_stride, n_src);
+}
+int specinv_misi_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->method == Method::Misi, SPECINV_ESTATE, "specinv_misi_init has not been called");
+  ENTER(plan);
+  return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
+}
+int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
+                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->method == Method::Misi, SPECINV_ESTATE, "specinv_misi_init has not been called");
+  ENTER(plan);
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }
 

@@ -255,7 +255,34 @@ class Plan:
         self._init(self.lib.specinv_admm_init, init_spec, mag, rho)
         self._method = "admm"
 
+    def misi_init(self, init_spec, mag, mixture, n_src):
+        """MISI on batch = n_mix * n_src items (item b * n_src + k: source k of mixture b): `init_spec` (batch, F, T) complex is
+        the start, `mag` the target (None: |init_spec|), `mixture` (n_mix, >= length) the mixtures - the first `length` samples
+        of each row are used.  Runs the first coupling step."""
+        self._sync_stream()
+        n_src = int(n_src)
+        if init_spec is None:
+            raise AssertionError("misi_init needs init_spec (misi() forms the mixture-phase start)")
+        spec = self._in(init_spec, self.cdtype, self._spec_shape())
+        m = None if mag is None else self._in(mag, self.dtype, self._spec_shape())
+        mix = self._in(mixture, self.dtype)
+        assert mix.dim() == 2, f"mixture must be (n_mix, length), got shape {tuple(mix.shape)}"
+        assert n_src < 1 or self.batch % n_src or mix.shape[0] == self.batch // n_src, \
+            f"mixture has {mix.shape[0]} rows, the plan holds {self.batch} items of {n_src} sources"
+        _lib.check(self.lib.specinv_misi_init(self._h, spec.data_ptr(), None if m is None else m.data_ptr(), mix.data_ptr(),
+                                              mix.shape[1], n_src))
+        self._method = "misi"
+
+    def misi_iterate(self, n_iter: int, eval_last: bool = False):
+        """`n_iter` MISI iterations (projection launch + coupling launch each); the evaluation sums of the last if asked."""
+        self._sync_stream()
+        sums = (C.c_double * 4)()
+        _lib.check(self.lib.specinv_misi_iterate(self._h, int(n_iter), int(eval_last), sums))
+        return list(sums) if eval_last else None
+
     def iterate(self, n_iter: int, eval_last: bool = False):
+        if self._method == "misi":
+            return self.misi_iterate(n_iter, eval_last)
         self._sync_stream()
         fn = self.lib.specinv_gla_iterate if self._method == "gla" else self.lib.specinv_admm_iterate
         sums = (C.c_double * 4)()
@@ -274,7 +301,7 @@ class Plan:
         Returns (iterations_done, [(iteration, metric, loss), ...])."""
         self._sync_stream()
         assert isinstance(metric, str) and metric.upper() in _lib.METRICS          # :167-168
-        fn = self.lib.specinv_gla_run if self._method == "gla" else self.lib.specinv_admm_run
+        fn = {"gla": self.lib.specinv_gla_run, "misi": self.lib.specinv_misi_run}.get(self._method, self.lib.specinv_admm_run)
         cap = max(1, int(max_iter) // max(1, int(eva_iter)) + 1)
         evals = (_lib.Eval * cap)()
         n_ev, done = C.c_int(0), C.c_int(0)
