@@ -180,7 +180,25 @@ int specinv_misi_iterate(specinv_plan* plan, int n_iter, int eval_last, double s
 int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
                      int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user);
 
-/* current waveform estimate status_dict['x'] (B, L) of the running GLA / ADMM / MISI state */
+/* ---- AGLA (Peer, Welker & Gerkmann 2022: accelerated Griffin-Lim) ------------------------ */
+/* Accelerated Griffin-Lim.  With P(x) = ISTFT(S m / (|S| + 1e-16)), S = STFT(x) - one Griffin-Lim iteration without momentum -
+ * and c_0 = ISTFT(start), iteration 1 sets t_1 = c_1 = d_1 = P(c_0) and iteration n > 1 computes, on signals of
+ * specinv_plan_length samples and in the plan's dtype,
+ *     y = P(c_{n-1});  t_n = (1 - gamma) d_{n-1} + gamma y;  c_n = t_n + alpha (t_n - t_{n-1});  d_n = t_n + beta (t_n - t_{n-1}).
+ * gamma = 1 is Fast Griffin-Lim (Perraudin, Balazs & Soendergaard 2013, the method of librosa and torchaudio): d is then never
+ * formed and beta has no effect; alpha = 0, gamma = 1 is Griffin-Lim without momentum.  init_spec / mag as specinv_gla_init
+ * (either may be NULL).  SPECINV_EINVAL, before the device is touched: alpha < 0, beta < 0, gamma <= 0, a NULL plan. */
+int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma);
+/* n_iter times: one projection launch, one extrapolation launch (k_agla_step).  An evaluating iteration's sums compare
+ * |STFT(c_{n-1})|, the signal that entered the projection, against the target.  SPECINV_ESTATE before specinv_agla_init;
+ * specinv_gla_iterate / _run, specinv_admm_iterate / _run and specinv_misi_iterate / _run return SPECINV_ESTATE on a plan in
+ * the AGLA state (they would drop the extrapolation), specinv_agla_iterate / _run on a plan in any other state. */
+int specinv_agla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]);
+int specinv_agla_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
+                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user);
+
+/* current waveform estimate status_dict['x'] (B, L) of the running GLA / ADMM / MISI state.  In the AGLA state: t_n, the
+ * method's result (ISTFT(start) before the first iteration) - not the extrapolated c_n the next projection reads */
 int specinv_get_wave(specinv_plan* plan, void* x_out);
 /* running state as (B, F, T) complex: which = 0 pre_spec (GLA) or X (ADMM), 1 U (ADMM), 2 Y = X + U (ADMM, always
  * available; X and U need specinv_plan_keep_state) - for state-parity tests */

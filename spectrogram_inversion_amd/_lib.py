@@ -83,6 +83,9 @@ SIGNATURES = {
     "specinv_misi_init": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int]),
     "specinv_misi_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),
     "specinv_misi_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
+    "specinv_agla_init": (C.c_int, [_P, _P, _P, _D, _D, _D]),
+    "specinv_agla_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),
+    "specinv_agla_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
     "specinv_get_wave": (C.c_int, [_P, _P]),
     "specinv_get_state_spec": (C.c_int, [_P, C.c_int, _P]),
     "specinv_gla_update": (C.c_int, [_P, _P, _P, _P, _D, _P, _P]),

@@ -33,8 +33,9 @@ struct alignas(sizeof(T) * V) MisiVec {
 
 // Offset of the tail samples that belong to samples n ... n + V - 1 of a row (hop % V == 0, n % V == 0: one hop-block) inside the
 // row's nchunks * nb * hop tail entries, -1 where the row's x is the whole value
-template <typename T>
-__device__ __forceinline__ int64_t misi_tail_offset(const MisiMixArgs<T>& a, int64_t n) {
+// (Args: MisiMixArgs, or another kernel's arguments with the same geometry fields - kernels_agla.h)
+template <typename Args>
+__device__ __forceinline__ int64_t misi_tail_offset(const Args& a, int64_t n) {
   const int blk = (int)(n / a.hop) + a.pb;                          // padded-signal hop-block
   const int smp = (int)(n % a.hop);
   // the chunk c whose frames begin at or before this block (chunks are skewed by a few frames around the even split)

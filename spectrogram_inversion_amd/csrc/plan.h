@@ -7,7 +7,7 @@
 
 namespace specinv {
 
-enum class Method { None, Gla, Admm, Misi };
+enum class Method { None, Gla, Admm, Misi, Agla };
 
 // the mel-inversion state of a plan (specinv_mel_nnls_setup; tu_mel_nnls.hip owns its layout)
 struct MelNnlsState;
@@ -46,6 +46,8 @@ struct PlanBase {
   virtual int admm_init(const void* init_spec, const void* mag, double rho) = 0;
   // MISI: Griffin-Lim without momentum on batch = n_mix * n_src items, coupled after every inverse transform (kernels_misi.h)
   virtual int misi_init(const void* init_spec, const void* mag, const void* mixture, int64_t mix_stride, int n_src) = 0;
+  // AGLA: the momentum-free projection, then the extrapolation of three signals on the signal state (kernels_agla.h)
+  virtual int agla_init(const void* init_spec, const void* mag, double alpha, double beta, double gamma) = 0;
   virtual int iterate(int n_iter, bool eval_last, double sums[4]) = 0;
   // evaluations whose result cannot influence the run (tol == 0, no callback) stay on the device and are
   // read back once at the end: deferred_slot >= 0 makes iterate() park its sums in that slot

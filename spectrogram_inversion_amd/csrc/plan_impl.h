@@ -17,6 +17,7 @@
 #include "objective_host.h"
 #include "kernels_big.h"
 #include "kernels_misi.h"
+#include "kernels_agla.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
 #include "plan.h"
@@ -97,6 +98,10 @@ struct PlanT final : PlanBase {
   T coef = 0;  // lr (GLA) or rho (ADMM)
   DevBuf misi_mix;                      // MISI: the mixtures, (batch / misi_k, length)
   int misi_k = 0;                       // ... and the sources per mixture
+  DevBuf agla_t, agla_d;                // AGLA: t_n and (gamma != 1 only) d_n, (batch, length) each
+  T agla_alpha = 0, agla_beta = 0, agla_gamma = 1, agla_omg = 0;   // ... alpha, beta, gamma, 1 - gamma, rounded once
+  bool agla_general = false;            // ... gamma != 1: d exists
+  int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
   FastState<T> fast;
   int tf_kind = -1, tf_mels = 0;
 
@@ -716,11 +721,63 @@ struct PlanT final : PlanBase {
     return misi_mix_launch<T>(a, B() / misi_k, stream);
   }
 
+  // AGLA (Peer, Welker & Gerkmann 2022; gamma = 1: the Fast Griffin-Lim of Perraudin, Balazs & Soendergaard 2013):
+  //   y = P(c_{n-1}) ; t_n = (1 - gamma) d_{n-1} + gamma y ; c_n = t_n + alpha (t_n - t_{n-1}) ; d_n = t_n + beta (t_n - t_{n-1})
+  // with P the momentum-free projection launch and c, t, d signals: c lives where the next launch reads it, t and d here
+  int agla_init(const void* init_spec, const void* magp, double alpha, double beta, double gamma) override {
+    SI_CHECK(alpha >= 0 && beta >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha, beta);
+    SI_CHECK(gamma > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma);
+    method = Method::None;
+    coef = T(0);
+    SI_TRY(init_common(init_spec, magp, fast::MODE_GLA, true));
+    agla_general = gamma != 1.0;
+    SI_TRY(agla_t.reserve((size_t)B() * length * sizeof(T)));
+    if (agla_general) SI_TRY(agla_d.reserve((size_t)B() * length * sizeof(T)));
+    else agla_d.release();
+    agla_alpha = (T)alpha;
+    agla_beta = (T)beta;
+    agla_gamma = (T)gamma;
+    agla_omg = (T)(1.0 - gamma);
+    agla_n = 0;
+    method = Method::Agla;
+    return SPECINV_OK;
+  }
+
+  // The extrapolation on the state the projection launch has just written and the next one reads (launch_mix's contract)
+  int launch_agla() {
+    AglaStepArgs<T> a{};
+    a.x = x.as<T>();
+    if (fast_path()) {
+      a.x = fast.state_rows();
+      a.tail = fast.state_tails();
+      if (a.tail != nullptr) {
+        a.n_frames = Tn();
+        a.nchunks = fast.nchunks;
+        a.skew = fast.skew;
+        a.hop = cfg.hop_length;
+        a.nb = fast.OV - 1;
+        a.pb = fast.OV / 2;
+      }
+    }
+    a.t = agla_t.as<T>();
+    a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
+    a.alpha = agla_alpha;
+    a.beta = agla_beta;
+    a.gamma = agla_gamma;
+    a.one_minus_gamma = agla_omg;
+    a.L = length;
+    a.first = agla_n == 0 ? 1 : 0;
+    SI_TRY(agla_step_launch<T>(a, B(), stream));
+    ++agla_n;
+    return SPECINV_OK;
+  }
+
   int iterate(int n_iter, bool eval_last, double s[4]) override {
     SI_CHECK(method != Method::None, SPECINV_ESTATE, "iterate called before gla_init/admm_init");
     SI_CHECK(n_iter >= 0, SPECINV_EINVAL, "n_iter < 0");
     if (n_iter == 0) return SPECINV_OK;
-    if (method == Method::Misi && n_iter > 1) {          // one projection launch, one mix launch per iteration
+    // MISI, AGLA: one projection launch, one launch on the signal per iteration
+    if ((method == Method::Misi || method == Method::Agla) && n_iter > 1) {
       for (int i = 0; i < n_iter; ++i) SI_TRY(iterate(1, eval_last && i == n_iter - 1, s));
       return SPECINV_OK;
     }
@@ -826,6 +883,8 @@ struct PlanT final : PlanBase {
     }
     // (an evaluating iteration's sums are the projection launch's: they describe the mixed signal that entered it)
     if (method == Method::Misi) SI_TRY(launch_mix());
+    // (AGLA alike: the sums compare |STFT(c_{n-1})|, the signal that entered the projection, against the target)
+    if (method == Method::Agla) SI_TRY(launch_agla());
     if (eval_last) {
       const int64_t n_part = fast_path() ? (int64_t)fast.n_partials
                              : big ? (int64_t)B() * Tn() * ceil_div(N() / 2 + 1, 256)
@@ -882,6 +941,10 @@ struct PlanT final : PlanBase {
   int get_wave(void* x_out) override {
     SI_CHECK(method != Method::None, SPECINV_ESTATE, "no running state");
     SI_CHECK(x_out, SPECINV_EINVAL, "null pointer");
+    if (method == Method::Agla && agla_n > 0) {          // AGLA's result is t_n; the state holds the extrapolated c_n
+      SI_HIP(hipMemcpyAsync(x_out, agla_t.p, (size_t)B() * length * sizeof(T), hipMemcpyDeviceToDevice, stream));
+      return SPECINV_OK;
+    }
     if (fast_path()) return fast.get_wave(*this, static_cast<T*>(x_out));
     SI_HIP(hipMemcpyAsync(x_out, x.p, (size_t)B() * length * sizeof(T), hipMemcpyDeviceToDevice, stream));
     return SPECINV_OK;

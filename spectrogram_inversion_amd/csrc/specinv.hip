@@ -219,6 +219,11 @@ int specinv_plan_force_generic(specinv_plan* plan, int on) {
   SI_CHECK((plan)->impl->method != Method::Misi, SPECINV_ESTATE,                                                      \
            name " on a plan in the MISI state would drop the coupling step: use specinv_misi_iterate / specinv_misi_run")
 
+// ... nor one in the AGLA state: the extrapolation would be dropped, and specinv_get_wave would return a stale t
+#define NOT_AGLA(plan, name)                                                                                           \
+  SI_CHECK((plan)->impl->method != Method::Agla, SPECINV_ESTATE,                                                      \
+           name " on a plan in the AGLA state would drop the extrapolation step: use specinv_agla_iterate / specinv_agla_run")
+
 #define ENTER(plan)                                 \
   PLAN_OR_FAIL(plan);                               \
   DeviceGuard guard_;                               \
@@ -253,6 +258,7 @@ int specinv_gla_init(specinv_plan* plan, const void* init_spec, const void* mag,
 int specinv_gla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   ENTER(plan);
   NOT_MISI(plan, "specinv_gla_iterate");
+  NOT_AGLA(plan, "specinv_gla_iterate");
   SI_CHECK(plan->impl->method == Method::Gla, SPECINV_ESTATE, "specinv_gla_init has not been called");
   return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
 }
@@ -260,6 +266,7 @@ int specinv_gla_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, 
                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
   ENTER(plan);
   NOT_MISI(plan, "specinv_gla_run");
+  NOT_AGLA(plan, "specinv_gla_run");
   SI_CHECK(plan->impl->method == Method::Gla, SPECINV_ESTATE, "specinv_gla_init has not been called");
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }
@@ -271,6 +278,7 @@ int specinv_admm_init(specinv_plan* plan, const void* init_spec, const void* mag
 int specinv_admm_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   ENTER(plan);
   NOT_MISI(plan, "specinv_admm_iterate");
+  NOT_AGLA(plan, "specinv_admm_iterate");
   SI_CHECK(plan->impl->method == Method::Admm, SPECINV_ESTATE, "specinv_admm_init has not been called");
   return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
 }
@@ -278,6 +286,7 @@ int specinv_admm_run(specinv_plan* plan, int max_iter, int eva_iter, double tol,
                      int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
   ENTER(plan);
   NOT_MISI(plan, "specinv_admm_run");
+  NOT_AGLA(plan, "specinv_admm_run");
   SI_CHECK(plan->impl->method == Method::Admm, SPECINV_ESTATE, "specinv_admm_init has not been called");
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }
@@ -297,6 +306,7 @@ int specinv_misi_init(specinv_plan* plan, const void* init_spec, const void* mag
 }
 int specinv_misi_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   PLAN_OR_FAIL(plan);
+  NOT_AGLA(plan, "specinv_misi_iterate");
   SI_CHECK(plan->impl->method == Method::Misi, SPECINV_ESTATE, "specinv_misi_init has not been called");
   ENTER(plan);
   return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
@@ -304,7 +314,29 @@ int specinv_misi_iterate(specinv_plan* plan, int n_iter, int eval_last, double s
 int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
                      int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
   PLAN_OR_FAIL(plan);
+  NOT_AGLA(plan, "specinv_misi_run");
   SI_CHECK(plan->impl->method == Method::Misi, SPECINV_ESTATE, "specinv_misi_init has not been called");
+  ENTER(plan);
+  return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
+}
+
+int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma) {
+  // (the argument errors before the device is touched; PlanT::agla_init repeats them for its own callers)
+  SI_CHECK(alpha >= 0 && beta >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha, beta);
+  SI_CHECK(gamma > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma);
+  ENTER(plan);
+  return plan->impl->agla_init(init_spec, mag, alpha, beta, gamma);
+}
+int specinv_agla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");
+  ENTER(plan);
+  return plan->impl->iterate(n_iter, eval_last != 0, sums_host);
+}
+int specinv_agla_run(specinv_plan* plan, int max_iter, int eva_iter, double tol, int metric, specinv_eval* evals_out,
+                     int* n_evals_out, int* iters_done_out, specinv_eval_cb cb, void* user) {
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");
   ENTER(plan);
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }

@@ -86,28 +86,32 @@ def _run_loop(plan, max_iter, tol, verbose, eva_iter, metric):
 _MAX_PLAN_BATCH = 65535
 
 
-def _slices(n_items):
-    return [(lo, min(n_items, lo + _MAX_PLAN_BATCH)) for lo in range(0, n_items, _MAX_PLAN_BATCH)]
+def _slices(n_items, per=None):
+    per = per or _MAX_PLAN_BATCH
+    return [(lo, min(n_items, lo + per)) for lo in range(0, n_items, per)]
 
 
-def _iterative_sliced(which, spec3, args, device, rdtype, coef, max_iter, tol, verbose, eva_iter, metric):
-    """griffin_lim / ADMM on a batch beyond one plan's 65 535 items: one plan per slice, stepped in lockstep; the metric and the
-    stop rule of `_training_loop` (torch_specinv/methods.py:181-190) are whole-batch quantities, so every evaluation adds the
-    slices' sums before the decision - what `distributed.run_loop_global` does across ranks, here across slices."""
+def _iterative_sliced(which, spec3, args, device, rdtype, coef, max_iter, tol, verbose, eva_iter, metric, per=None):
+    """griffin_lim / ADMM / accelerated_griffin_lim (`which` = "gla", "admm", "agla"; `coef` the parameters of `Plan.<which>_init`
+    after the two spectrogram arguments, a tuple where there are several) on a batch beyond one plan's 65 535 items (`per`): one
+    plan per slice, stepped in lockstep; the metric and the stop rule of `_training_loop` (torch_specinv/methods.py:181-190) are
+    whole-batch quantities, so every evaluation adds the slices' sums before the decision - what `distributed.run_loop_global`
+    does across ranks, here across slices."""
     from .metrics import _from_sums
     from .plan import Plan
     assert eva_iter > 0 and max_iter > 0 and tol >= 0
     assert isinstance(metric, str) and metric.upper() in _lib.METRICS
     name = metric.upper()
+    coefs = coef if isinstance(coef, tuple) else (coef,)
     plans = []
-    for lo, hi in _slices(spec3.shape[0]):
+    for lo, hi in _slices(spec3.shape[0], per):
         p = Plan(args, hi - lo, spec3.shape[2], rdtype, device)
         part = spec3[lo:hi]
         init = getattr(p, which + "_init")
         if part.is_complex():
-            init(part, None, coef)
+            init(part, None, *coefs)
         else:
-            init(None, part, coef)
+            init(None, part, *coefs)
         plans.append(p)
     done, init_loss, previous = 0, None, None
     with tqdm(total=max_iter, disable=not verbose) as pbar:

@@ -280,9 +280,28 @@ class Plan:
         _lib.check(self.lib.specinv_misi_iterate(self._h, int(n_iter), int(eval_last), sums))
         return list(sums) if eval_last else None
 
+    def agla_init(self, init_spec, mag, alpha, beta, gamma):
+        """Accelerated Griffin-Lim (include/specinv.h: specinv_agla_init): `init_spec` (batch, F, T) complex is the start (None:
+        `phase_init(mag)` on the device), `mag` the target (None: |init_spec|); alpha, beta >= 0, gamma > 0."""
+        self._sync_stream()
+        spec = None if init_spec is None else self._in(init_spec, self.cdtype, self._spec_shape())
+        m = None if mag is None else self._in(mag, self.dtype, self._spec_shape())
+        _lib.check(self.lib.specinv_agla_init(self._h, None if spec is None else spec.data_ptr(), None if m is None else m.data_ptr(),
+                                              float(alpha), float(beta), float(gamma)))
+        self._method = "agla"
+
+    def agla_iterate(self, n_iter: int, eval_last: bool = False):
+        """`n_iter` AGLA iterations (projection launch + extrapolation launch each); the evaluation sums of the last if asked."""
+        self._sync_stream()
+        sums = (C.c_double * 4)()
+        _lib.check(self.lib.specinv_agla_iterate(self._h, int(n_iter), int(eval_last), sums))
+        return list(sums) if eval_last else None
+
     def iterate(self, n_iter: int, eval_last: bool = False):
         if self._method == "misi":
             return self.misi_iterate(n_iter, eval_last)
+        if self._method == "agla":
+            return self.agla_iterate(n_iter, eval_last)
         self._sync_stream()
         fn = self.lib.specinv_gla_iterate if self._method == "gla" else self.lib.specinv_admm_iterate
         sums = (C.c_double * 4)()
@@ -301,7 +320,8 @@ class Plan:
         Returns (iterations_done, [(iteration, metric, loss), ...])."""
         self._sync_stream()
         assert isinstance(metric, str) and metric.upper() in _lib.METRICS          # :167-168
-        fn = {"gla": self.lib.specinv_gla_run, "misi": self.lib.specinv_misi_run}.get(self._method, self.lib.specinv_admm_run)
+        fn = {"gla": self.lib.specinv_gla_run, "misi": self.lib.specinv_misi_run,
+              "agla": self.lib.specinv_agla_run}.get(self._method, self.lib.specinv_admm_run)
         cap = max(1, int(max_iter) // max(1, int(eva_iter)) + 1)
         evals = (_lib.Eval * cap)()
         n_ev, done = C.c_int(0), C.c_int(0)
@@ -317,6 +337,7 @@ class Plan:
         return done.value, [(evals[i].iteration, evals[i].metric, evals[i].loss) for i in range(n_ev.value)]
 
     def wave(self) -> torch.Tensor:
+        """The running method's waveform estimate (`specinv_get_wave`); after `agla_init` that is t_n, AGLA's result."""
         self._sync_stream()
         out = torch.empty((self.batch, self.length), dtype=self.dtype, device=self.device)
         _lib.check(self.lib.specinv_get_wave(self._h, out.data_ptr()))
