@@ -222,6 +222,19 @@ int specinv_admm_update_adjoint(specinv_plan* plan, const void* gYn, const void*
 int specinv_istft_adjoint(specinv_plan* plan, const void* g_x, void* g_spec_out);
 /* adjoint of specinv_stft: cotangent of the spectrogram -> cotangent of x (B, length) */
 int specinv_stft_adjoint(specinv_plan* plan, const void* g_spec, int64_t length, void* g_x_out);
+/* ---- MISI's backward sweep (misi_unfolded; csrc/kernels_misi_adjoint.h) ------------------- */
+/* Both calls are stateless: they work on a plan in any method state, write only scratch buffers and leave a running method's
+ * state as it is.  batch = n_mix * n_src items, item b * n_src + k source k of mixture b (specinv_misi_init).  SPECINV_EINVAL,
+ * before anything is enqueued: a NULL pointer, n_src < 1, a batch that is no multiple of n_src. */
+/* adjoint of the coupling step x_k += (mix - sum_j x_j) / n_src: g_inout (batch, length) holds the cotangents of the coupled
+ * signals and receives g_k - c, c = (1 / n_src) sum_k g_k; c is added to gmix_accum (n_mix, length). */
+int specinv_misi_mix_adjoint(specinv_plan* plan, int n_src, void* g_inout, void* gmix_accum);
+/* adjoint of one MISI iteration x_n = mix_step(ISTFT(mag * S / (|S| + 1e-16))), S = STFT(x_prev): g_inout (batch, length) holds
+ * the cotangent of x_n and receives that of x_prev (batch, length); gmix_accum (n_mix, length) and gmag_fm_accum accumulate the
+ * mixture's and the magnitude's.  mag_fm and gmag_fm_accum are frame-major, (batch, n_frames, n_freq): the transposes of the
+ * caller-layout arrays, made once per sweep and not once per iteration.  S is recomputed from x_prev. */
+int specinv_misi_step_adjoint(specinv_plan* plan, int n_src, const void* x_prev, const void* mag_fm, void* g_inout,
+                              void* gmix_accum, void* gmag_fm_accum);
 /* adjoint of specinv_phase_init: gmag += d/dmag of <g_spec, phase_init(mag)> */
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum);
 

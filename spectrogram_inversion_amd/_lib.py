@@ -95,6 +95,8 @@ SIGNATURES = {
     "specinv_istft_adjoint": (C.c_int, [_P, _P, _P]),
     "specinv_stft_adjoint": (C.c_int, [_P, _P, _I64, _P]),
     "specinv_phase_init_adjoint": (C.c_int, [_P, _P, _P, _P]),
+    "specinv_misi_mix_adjoint": (C.c_int, [_P, C.c_int, _P, _P]),
+    "specinv_misi_step_adjoint": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "specinv_rtisi_run": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P]),
     "specinv_rtisi_record_elems": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "specinv_rtisi_run_recorded": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P, _P]),

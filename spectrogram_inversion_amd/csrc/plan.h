@@ -70,6 +70,9 @@ struct PlanBase {
   virtual int istft_adjoint(const void* g_x, void* g_spec_out) = 0;
   virtual int stft_adjoint(const void* g_spec, int64_t len, void* g_x_out) = 0;
   virtual int phase_init_adjoint(const void* mag, const void* g_spec, void* gmag) = 0;
+  // MISI's backward sweep (kernels_misi_adjoint.h): the coupling step's adjoint, and one whole unfolded iteration's; stateless
+  virtual int misi_mix_adjoint(int n_src, void* g, void* gmix) = 0;
+  virtual int misi_step_adjoint(int n_src, const void* x_prev, const void* mag_fm, void* g, void* gmix, void* gmag_fm) = 0;
 
   virtual int rtisi_run(const void* mag, int look_ahead, int asym, int max_iter, double alpha, void* x_out) = 0;
   virtual int rtisi_record_elems(int look_ahead, int max_iter, int64_t* out) = 0;

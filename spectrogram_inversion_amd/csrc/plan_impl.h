@@ -18,6 +18,7 @@
 #include "kernels_big.h"
 #include "kernels_misi.h"
 #include "kernels_agla.h"
+#include "kernels_misi_adjoint.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
 #include "plan.h"
@@ -61,6 +62,7 @@ struct PlanT final : PlanBase {
   using C = cplx<T>;
   DevBuf window, tw, env;
   DevBuf x, frames, specA, specB, mag, partials, sums, tmp_spec, tmp_real;
+  DevBuf tmp_spec2;                     // misi_step_adjoint: the recomputed spectrum beside the cotangent's in tmp_spec
   DevBuf rt_state;                      // RTISI per-item state
   DevBuf rs_state;                      // ... of the streaming recursion (survives between pushes)
   RtisiStream<T> rstream;
@@ -1062,6 +1064,52 @@ struct PlanT final : PlanBase {
                        cfg.hop_length);
     SI_HIP(hipGetLastError());
     return SPECINV_OK;
+  }
+
+  // M^T alone: c = mean_k g_k ; gmix += c ; g_k -= c   (x_0 = M(B C0): the last step of the sweep)
+  int misi_mix_adjoint(int n_src, void* g, void* gmix) override {
+    SI_CHECK(g && gmix, SPECINV_EINVAL, "null pointer");
+    SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+    SI_CHECK(B() % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)", B(), n_src);
+    MisiMixAdjArgs<T> a{};
+    a.g = static_cast<T*>(g);
+    a.gmix = static_cast<T*>(gmix);
+    a.L = length;
+    a.K = n_src;
+    return misi_mix_adjoint_launch<T>(a, B() / n_src, stream);
+  }
+
+  // The adjoint of one unfolded MISI iteration x_n = M(B(m A x_{n-1} / (|A x_{n-1}| + 1e-16))) in four stages
+  // (kernels_misi_adjoint.h): g, the cotangent of x_n, becomes that of x_{n-1}; the mixture's and the magnitude's are accumulated.
+  // Only scratch is written (tmp_spec, tmp_spec2, the frames of grad_from_spec): a running method's state is not touched.
+  int misi_step_adjoint(int n_src, const void* x_prev, const void* mag_fm, void* g, void* gmix, void* gmag_fm) override {
+    SI_CHECK(x_prev && mag_fm && g && gmix && gmag_fm, SPECINV_EINVAL, "null pointer");
+    SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+    SI_CHECK(B() % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)", B(), n_src);
+    const int64_t ns = nspec();
+    SI_TRY(tmp_spec.reserve(ns * sizeof(C)));
+    SI_TRY(tmp_spec2.reserve(ns * sizeof(C)));
+    MisiMixAdjArgs<T> a{};
+    a.g = static_cast<T*>(g);
+    a.gmix = static_cast<T*>(gmix);
+    a.env = env.as<T>();
+    a.L = length;
+    a.K = n_src;
+    SI_TRY(misi_mix_adjoint_launch<T>(a, B() / n_src, stream));                                       // u = M^T g / env
+    SI_TRY(stft_internal(a.g, length, tmp_spec.as<C>(), SPECINV_PAD_CONSTANT, T(1)));                // Y
+    SI_TRY(stft_internal(static_cast<const T*>(x_prev), length, tmp_spec2.as<C>()));                 // R
+    MisiProjAdjArgs<T> p{};
+    p.y = tmp_spec.as<C>();
+    p.r = tmp_spec2.as<C>();
+    p.m = static_cast<const T*>(mag_fm);
+    p.gm = static_cast<T*>(gmag_fm);
+    p.total = ns;
+    p.F = n_freq;
+    p.n_fft = N();
+    p.onesided = cfg.onesided;
+    p.inv_scale = fc.inv_scale;
+    SI_TRY(misi_proj_adjoint_launch<T>(p, stream));                                                  // gR, halved; gm
+    return grad_from_spec(tmp_spec.as<C>(), a.g, fc.fwd_scale, length);                              // A^T
   }
 
   // RTISI-LA stages its target and its committed frames in the buffers that hold the target / frame scratch of a

@@ -388,6 +388,27 @@ int specinv_stft_adjoint(specinv_plan* plan, const void* g_spec, int64_t length,
   ENTER(plan);
   return plan->impl->stft_adjoint(g_spec, length, g_x_out);
 }
+int specinv_misi_mix_adjoint(specinv_plan* plan, int n_src, void* g_inout, void* gmix_accum) {
+  // (the argument errors before the device is touched; PlanT repeats them for its own callers)
+  SI_CHECK(g_inout && gmix_accum, SPECINV_EINVAL, "specinv_misi_mix_adjoint: NULL %s", g_inout ? "gmix_accum" : "g_inout");
+  SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->cfg.batch % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)",
+           plan->impl->cfg.batch, n_src);
+  ENTER(plan);
+  return plan->impl->misi_mix_adjoint(n_src, g_inout, gmix_accum);
+}
+int specinv_misi_step_adjoint(specinv_plan* plan, int n_src, const void* x_prev, const void* mag_fm, void* g_inout,
+                              void* gmix_accum, void* gmag_fm_accum) {
+  SI_CHECK(x_prev && mag_fm && g_inout && gmix_accum && gmag_fm_accum, SPECINV_EINVAL, "specinv_misi_step_adjoint: NULL %s",
+           !x_prev ? "x_prev" : !mag_fm ? "mag_fm" : !g_inout ? "g_inout" : !gmix_accum ? "gmix_accum" : "gmag_fm_accum");
+  SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->cfg.batch % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)",
+           plan->impl->cfg.batch, n_src);
+  ENTER(plan);
+  return plan->impl->misi_step_adjoint(n_src, x_prev, mag_fm, g_inout, gmix_accum, gmag_fm_accum);
+}
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum) {
   ENTER(plan);
   return plan->impl->phase_init_adjoint(mag, g_spec, gmag_accum);

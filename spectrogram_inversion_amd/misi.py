@@ -5,7 +5,8 @@ One iteration is the Griffin-Lim projection without momentum on the B * K items,
 
     e = (mix - sum_k y_k) / K ;   x_k = y_k + e
 
-on the plan's own signal state (`specinv_misi_*`, csrc/kernels_misi.h).  Not part of the reference's surface.
+on the plan's own signal state (`specinv_misi_*`, csrc/kernels_misi.h).  `misi_unfolded` is a fixed number of these iterations as a
+differentiable layer (csrc/kernels_misi_adjoint.h).  Not part of the reference's surface.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from . import _lib
 from .methods import _MAX_PLAN_BATCH, _no_complex_window, _run_loop
 from .plan import Plan, args_helper, get_plan, require_gpu, trim_plan_cache
 
-__all__ = ["misi"]
+__all__ = ["misi", "misi_unfolded"]
 
 _NARROW = {torch.float16: torch.float32, torch.bfloat16: torch.float32, torch.complex32: torch.complex64}
 _REAL_OF = {torch.complex64: torch.float32, torch.complex128: torch.float64}
@@ -71,16 +72,7 @@ def _run_sliced(specs4, mix2, args, device, rdtype, per, max_iter, tol, verbose,
     return torch.cat([p.wave() for p in plans], 0)
 
 
-def misi(specs, mixture, max_iter=200, tol=1e-6, verbose=True, eva_iter=10, metric="sc", **stft_kwargs):
-    r"""Waveforms (K, L) / (B, K, L) of K sources whose sum is the mixture, from their spectrograms.
-
-    `specs` is (K, F, T) or (B, K, F, T): magnitudes - the iteration then starts from the mixture's phase - or a complex
-    spectrogram to start from (its modulus is the target).  `mixture` is (L_m,) or (B, L_m) with L_m >= L, the length the
-    spectrograms invert to; samples beyond L are ignored.  `max_iter`, `tol`, `eva_iter`, `metric`, `verbose` and
-    `**stft_kwargs` are those of `griffin_lim`; there is no momentum.  The sum of the result over its source axis equals
-    `mixture[..., :L]` to rounding.  CPU tensors are computed on the current HIP device and come back to the CPU; float16 /
-    bfloat16 are computed in float32.  Not differentiable.
-    """
+def _check_tensors(specs, mixture):
     if not isinstance(specs, torch.Tensor) or not isinstance(mixture, torch.Tensor):
         raise TypeError("specs and mixture must be torch.Tensors")
     if mixture.is_complex():
@@ -90,8 +82,11 @@ def misi(specs, mixture, max_iter=200, tol=1e-6, verbose=True, eva_iter=10, metr
     if mixture.dim() != specs.dim() - 2:
         raise ValueError(f"mixture must be {'(L,)' if specs.dim() == 3 else '(B, L)'} for specs of shape {tuple(specs.shape)}, "
                          f"got shape {tuple(mixture.shape)}")
-    if torch.is_grad_enabled() and (specs.requires_grad or mixture.requires_grad):
-        raise NotImplementedError("misi is not differentiable; detach the inputs")
+
+
+def _prepare(specs, mixture, stft_kwargs):
+    """The checked arguments in the form the plan takes, all that needs no device: (specs4 (B, K, F, T), mix2 (B, L_m), args,
+    rdtype, L, half) - float16 / bfloat16 widened to float32 (`half`: the dtype to return), a batch axis added where absent."""
     half = specs.dtype if specs.dtype in _NARROW else None
     if half is not None:
         specs = specs.to(_NARROW[specs.dtype])
@@ -121,6 +116,36 @@ def misi(specs, mixture, max_iter=200, tol=1e-6, verbose=True, eva_iter=10, metr
     if mix2.shape[1] < L:
         raise ValueError(f"mixture of shape {tuple(mixture.shape)} is shorter than the {L} samples specs of shape "
                          f"{tuple(specs.shape)} invert to")
+    return specs4, mix2, args, rdtype, L, half
+
+
+def _finish(x, specs, half):
+    """(B * K, L) on the device -> the caller's shape, device and dtype."""
+    B, K = (1, specs.shape[0]) if specs.dim() == 3 else specs.shape[:2]
+    x = x.reshape(B, K, -1)
+    if specs.dim() == 3:
+        x = x.squeeze(0)
+    x = x.to(specs.device)
+    if half is None:
+        return x
+    return x.to(torch.float16 if half == torch.complex32 else half)
+
+
+def misi(specs, mixture, max_iter=200, tol=1e-6, verbose=True, eva_iter=10, metric="sc", **stft_kwargs):
+    r"""Waveforms (K, L) / (B, K, L) of K sources whose sum is the mixture, from their spectrograms.
+
+    `specs` is (K, F, T) or (B, K, F, T): magnitudes - the iteration then starts from the mixture's phase - or a complex
+    spectrogram to start from (its modulus is the target).  `mixture` is (L_m,) or (B, L_m) with L_m >= L, the length the
+    spectrograms invert to; samples beyond L are ignored.  `max_iter`, `tol`, `eva_iter`, `metric`, `verbose` and
+    `**stft_kwargs` are those of `griffin_lim`; there is no momentum.  The sum of the result over its source axis equals
+    `mixture[..., :L]` to rounding.  CPU tensors are computed on the current HIP device and come back to the CPU; float16 /
+    bfloat16 are computed in float32.  Not differentiable: `misi_unfolded` is the form to train through.
+    """
+    _check_tensors(specs, mixture)
+    if torch.is_grad_enabled() and (specs.requires_grad or mixture.requires_grad):
+        raise NotImplementedError("misi is not differentiable; detach the inputs")
+    specs4, mix2, args, rdtype, L, half = _prepare(specs, mixture, stft_kwargs)
+    B, K, F, T = specs4.shape
     device = require_gpu(specs.device)
     specs4, mix2 = specs4.to(device), mix2.to(device)
     if B * K > _MAX_PLAN_BATCH:
@@ -132,10 +157,87 @@ def misi(specs, mixture, max_iter=200, tol=1e-6, verbose=True, eva_iter=10, metr
         _run_loop(plan, max_iter, tol, verbose, eva_iter, metric)
         x = plan.wave()
     trim_plan_cache()
-    x = x.reshape(B, K, L)
-    if specs.dim() == 3:
-        x = x.squeeze(0)
-    x = x.to(specs.device)
-    if half is None:
-        return x
-    return x.to(torch.float16 if half == torch.complex32 else half)
+    return _finish(x, specs, half)
+
+
+class _MisiUnfoldedFn(torch.autograd.Function):
+    """`n_iter` MISI iterations as one differentiable layer.  The forward pass is the inference kernels with the iterates recorded
+    as signals, x_0 ... x_{N-1} (N B K L reals where recorded spectra would be N B K F T complex); the backward sweep recomputes
+    each spectrum from its signal and runs one `specinv_misi_step_adjoint` per iteration (csrc/kernels_misi_adjoint.h)."""
+
+    @staticmethod
+    def forward(ctx, specs4, mix2, plan, n_iter):
+        B, K, F, T = specs4.shape
+        specs3 = specs4.detach().reshape(B * K, F, T).contiguous()
+        mix = mix2.detach().contiguous()
+        init, mag = _start(plan, specs3, mix, K)
+        plan.misi_init(init, mag, mix, K)
+        waves = []
+        for _ in range(n_iter):
+            waves.append(plan.wave())                                  # x_{n-1}: what the next projection launch reads
+            plan.misi_iterate(1)
+        ctx.plan, ctx.n_src = plan, K
+        ctx.save_for_backward(specs3, mix, *waves)
+        return plan.wave()
+
+    @staticmethod
+    def backward(ctx, g_y):
+        plan, K = ctx.plan, ctx.n_src
+        specs3, mix, *waves = ctx.saved_tensors
+        n_mix, L = plan.batch // K, plan.length
+        real_in = not specs3.is_complex()
+        mag = specs3 if real_in else specs3.abs()
+        g = g_y.detach().to(plan.dtype).clone(memory_format=torch.contiguous_format)   # (the sweep works in place)
+        gmix = torch.zeros((n_mix, L), dtype=plan.dtype, device=plan.device)
+        mag_fm = mag.transpose(1, 2).contiguous()                      # frame-major once, not once per iteration
+        gm_fm = torch.zeros_like(mag_fm)
+        for x_prev in reversed(waves):
+            plan.misi_step_adjoint(K, x_prev, mag_fm, g, gmix, gm_fm)
+        plan.misi_mix_adjoint(K, g, gmix)                              # x_0 = M(ISTFT(C0))
+        gc = plan.istft_adjoint(g)
+        gm = gm_fm.transpose(1, 2)
+        if real_in:
+            # C0 = specs U, U = R / |R| the phase of R = STFT(mixture[:L]) (1, with no gradient, where R = 0)
+            r = plan.stft(mix[:, :L].repeat_interleave(K, dim=0).contiguous())
+            a = r.abs()
+            zero = a == 0
+            u = torch.where(zero, torch.ones_like(r), r / a)
+            g_specs = gm + (gc.real * u.real + gc.imag * u.imag)
+            if ctx.needs_input_grad[1]:
+                gu = gc * mag
+                g_r = torch.where(zero, torch.zeros_like(r), (gu - u * (gu.real * u.real + gu.imag * u.imag)) / a)
+                gmix += plan.stft_adjoint(g_r, L).reshape(n_mix, K, L).sum(1)
+        else:
+            unit = torch.where(mag > 0, specs3 / mag, torch.zeros_like(specs3))
+            g_specs = gc + gm * unit                                   # target = |C0| (autograd._input_grad)
+        g_mix = None
+        if ctx.needs_input_grad[1]:
+            g_mix = torch.zeros_like(mix)                              # samples beyond L never enter
+            g_mix[:, :L] = gmix
+        return g_specs.reshape(n_mix, K, *specs3.shape[1:]), g_mix, None, None
+
+
+def misi_unfolded(specs, mixture, n_iter=5, **stft_kwargs):
+    r"""`n_iter` MISI iterations as a layer to train through (Wang, Le Roux & Hershey 2018): `misi` with a fixed iteration count
+    and gradients.
+
+    `specs`, `mixture`, `**stft_kwargs`, the start, shapes, dtypes and devices are those of `misi`; there is no stop rule.  Without
+    a gradient to compute the result is `misi(specs, mixture, max_iter=n_iter, tol=0, verbose=False, **stft_kwargs)`.  With grad
+    mode on and `specs` or `mixture` requiring grad, the same kernels run and the result carries gradients to `specs` (magnitudes:
+    directly and through the start; a complex start: through the start and its modulus, the target) and to `mixture` (through
+    every coupling step and, for magnitudes, through the start's phase; samples beyond L get zero).  At most 65535 items (B * K).
+    """
+    _check_tensors(specs, mixture)
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 1:
+        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
+    specs4, mix2, args, rdtype, L, half = _prepare(specs, mixture, stft_kwargs)
+    B, K, F, T = specs4.shape
+    if B * K > _MAX_PLAN_BATCH:
+        raise ValueError(f"specs of shape {tuple(specs.shape)} hold {B * K} items, misi_unfolded takes at most {_MAX_PLAN_BATCH}")
+    if not (torch.is_grad_enabled() and (specs.requires_grad or mixture.requires_grad)):
+        return misi(specs, mixture, max_iter=n_iter, tol=0, verbose=False, **stft_kwargs)
+    device = require_gpu(specs.device)
+    plan = get_plan(args, B * K, T, rdtype, device)
+    x = _MisiUnfoldedFn.apply(specs4.to(device), mix2.to(device), plan, n_iter)
+    trim_plan_cache()
+    return _finish(x, specs, half)

@@ -402,6 +402,40 @@ class Plan:
         self._sync_stream()
         _lib.check(self.lib.specinv_phase_init_adjoint(self._h, mag.data_ptr(), g_spec.data_ptr(), gmag.data_ptr()))
 
+    def _inout(self, t: torch.Tensor, shape, what):
+        """A tensor the library updates in place: it has to be the caller's own memory, so nothing is converted."""
+        assert t.dtype == self.dtype and t.device == self.device and t.is_contiguous() and not t.requires_grad, \
+            f"{what} must be a contiguous {self.dtype} tensor on {self.device} that requires no grad"
+        assert tuple(t.shape) == tuple(shape), f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}"
+        return t.data_ptr()
+
+    def _mix_rows(self, n_src):
+        # (an n_src the library refuses gets its error from there)
+        return self.batch // n_src if n_src >= 1 and self.batch % n_src == 0 else 0
+
+    def misi_mix_adjoint(self, n_src, g, gmix):
+        """Adjoint of MISI's coupling step, in place: with c = mean_k g_k over the `n_src` sources of a mixture, `g`
+        (batch, length) becomes g_k - c and `gmix` (batch / n_src, length) gains c."""
+        self._sync_stream()
+        n_src = int(n_src)
+        gp = self._inout(g, (self.batch, self.length), "g")
+        mp = self._inout(gmix, (self._mix_rows(n_src) or gmix.shape[0], self.length), "gmix")
+        _lib.check(self.lib.specinv_misi_mix_adjoint(self._h, n_src, gp, mp))
+
+    def misi_step_adjoint(self, n_src, x_prev, mag_fm, g, gmix, gmag_fm):
+        """Adjoint of one MISI iteration x_prev -> x_n (`specinv_misi_step_adjoint`), in place: `g` (batch, length), the
+        cotangent of x_n, becomes that of `x_prev`; `gmix` (batch / n_src, length) and `gmag_fm` gain the mixture's and the
+        magnitude's.  `mag_fm` and `gmag_fm` are frame-major, (batch, n_frames, n_freq)."""
+        self._sync_stream()
+        n_src = int(n_src)
+        fm = (self.batch, self.n_frames, self.n_freq)
+        x_prev = self._in(x_prev, self.dtype, (self.batch, self.length))
+        mag_fm = self._in(mag_fm, self.dtype, fm)
+        gp = self._inout(g, (self.batch, self.length), "g")
+        mp = self._inout(gmix, (self._mix_rows(n_src) or gmix.shape[0], self.length), "gmix")
+        _lib.check(self.lib.specinv_misi_step_adjoint(self._h, n_src, x_prev.data_ptr(), mag_fm.data_ptr(), gp, mp,
+                                                      self._inout(gmag_fm, fm, "gmag_fm")))
+
     def rtisi(self, mag, look_ahead, asymmetric_window, max_iter, alpha) -> torch.Tensor:
         self._sync_stream()
         mag = self._in(mag, self.dtype, self._spec_shape())
