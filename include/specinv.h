@@ -189,6 +189,12 @@ int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol,
  * formed and beta has no effect; alpha = 0, gamma = 1 is Griffin-Lim without momentum.  init_spec / mag as specinv_gla_init
  * (either may be NULL).  SPECINV_EINVAL, before the device is touched: alpha < 0, beta < 0, gamma <= 0, a NULL plan. */
 int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma);
+/* specinv_agla_init with a schedule: iteration n takes entry min(n, n_sched) - 1 of the three host arrays of n_sched doubles (they
+ * are copied; iteration 1 does not extrapolate, entry 0 has no effect).  Each entry is rounded to the plan's dtype once; d exists
+ * iff some gamma entry != 1.  specinv_agla_init is the case n_sched = 1.  SPECINV_EINVAL, before the device is touched: n_sched < 1,
+ * a NULL array, an alpha or beta entry < 0, a gamma entry <= 0, a NULL plan. */
+int specinv_agla_init_sched(specinv_plan* plan, const void* init_spec, const void* mag, int n_sched, const double* alpha,
+                            const double* beta, const double* gamma);
 /* n_iter times: one projection launch, one extrapolation launch (k_agla_step).  An evaluating iteration's sums compare
  * |STFT(c_{n-1})|, the signal that entered the projection, against the target.  SPECINV_ESTATE before specinv_agla_init;
  * specinv_gla_iterate / _run, specinv_admm_iterate / _run and specinv_misi_iterate / _run return SPECINV_ESTATE on a plan in
@@ -235,6 +241,31 @@ int specinv_misi_mix_adjoint(specinv_plan* plan, int n_src, void* g_inout, void*
  * caller-layout arrays, made once per sweep and not once per iteration.  S is recomputed from x_prev. */
 int specinv_misi_step_adjoint(specinv_plan* plan, int n_src, const void* x_prev, const void* mag_fm, void* g_inout,
                               void* gmix_accum, void* gmag_fm_accum);
+/* the backward sweep of agla_unfolded (csrc/kernels_agla_adjoint.h), one call per iteration n = N ... 2, then the closing call.
+ * Stateless as the MISI entries above.  All signals are (batch, length) in the plan's dtype.  The sweep's state: a_inout, the
+ * cotangent of t_n (complete); gc_inout and gd_inout, those of c_n and d_n (gd_inout NULL: the form for schedules whose every gamma
+ * is 1, where it is identically 0; gamma_n must then be 1).  t_n, t_nm1, t_nm2 are the recorded results of iterations n, n - 1,
+ * n - 2 (t_nm2 NULL: n = 2).  coef (host) = {alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1}}, each rounded to the plan's dtype
+ * once; the last two are not read for n = 2.  With s = a + (1 + alpha_n) gc + (1 + beta_n) gd and delta = t_n - t_nm1:
+ *   dots_dev_out (3 doubles on the device) = {<gc, delta>, <gd, delta>, <s, t_n - d_{n-1}> / gamma_n}, the gradients of alpha_n,
+ *     beta_n, gamma_n, summed over all batch * length samples in double, in a fixed order (no atomics; nothing is read back);
+ *   a <- -alpha_n gc - beta_n gd ;  gd <- (1 - gamma_n) s ;  gc <- gamma_n s / envelope ;
+ *   c_prev_out <- c_{n-1} = t_nm1 + alpha_{n-1} (t_nm1 - t_nm2) (n = 2: t_nm1); d_{n-1} is formed likewise with beta_{n-1}.
+ * SPECINV_EINVAL before anything is enqueued: a NULL pointer other than t_nm2 / gd_inout, alpha or beta < 0, gamma <= 0, gamma_n != 1
+ * without gd_inout. */
+int specinv_agla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                                void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out);
+/* ... followed by the adjoint of the projection of iteration n at c_prev_out (the stages of specinv_misi_step_adjoint after its
+ * coupling step): gc_inout receives the cotangent of c_{n-1}, gmag_fm_accum accumulates the magnitude's; mag_fm and gmag_fm_accum are
+ * frame-major, (batch, n_frames, n_freq). */
+int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                              void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out,
+                              const void* mag_fm, void* gmag_fm_accum);
+/* the closing step, iteration 1: t_1 = c_1 = d_1 = P(c_0), c0 = ISTFT(start) as recorded.  gc_inout <- (a + gc + gd) / envelope
+ * (gd NULL: absent), then the projection's adjoint at c0: gc_inout receives the cotangent of c0, which specinv_istft_adjoint takes
+ * to the start. */
+int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
+                               void* gmag_fm_accum);
 /* adjoint of specinv_phase_init: gmag += d/dmag of <g_spec, phase_init(mag)> */
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum);
 

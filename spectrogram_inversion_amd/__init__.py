@@ -20,5 +20,5 @@ from .streaming import RTISIStream                                      # noqa: 
 from .mel import mel_filterbank                                         # noqa: E402,F401
 from .mel_inverse import mel_to_stft, mel_to_audio                      # noqa: E402,F401
 from .misi import misi, misi_unfolded                                   # noqa: E402,F401
-from .agla import accelerated_griffin_lim                               # noqa: E402,F401
+from .agla import accelerated_griffin_lim, agla_unfolded                # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

@@ -84,6 +84,7 @@ SIGNATURES = {
     "specinv_misi_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),
     "specinv_misi_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
     "specinv_agla_init": (C.c_int, [_P, _P, _P, _D, _D, _D]),
+    "specinv_agla_init_sched": (C.c_int, [_P, _P, _P, C.c_int, _DP, _DP, _DP]),
     "specinv_agla_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),
     "specinv_agla_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
     "specinv_get_wave": (C.c_int, [_P, _P]),
@@ -97,6 +98,9 @@ SIGNATURES = {
     "specinv_phase_init_adjoint": (C.c_int, [_P, _P, _P, _P]),
     "specinv_misi_mix_adjoint": (C.c_int, [_P, C.c_int, _P, _P]),
     "specinv_misi_step_adjoint": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "specinv_agla_extrap_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P]),
+    "specinv_agla_step_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P, _P, _P]),
+    "specinv_agla_first_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "specinv_rtisi_run": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P]),
     "specinv_rtisi_record_elems": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "specinv_rtisi_run_recorded": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P, _P]),

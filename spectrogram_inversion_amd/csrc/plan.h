@@ -47,7 +47,9 @@ struct PlanBase {
   // MISI: Griffin-Lim without momentum on batch = n_mix * n_src items, coupled after every inverse transform (kernels_misi.h)
   virtual int misi_init(const void* init_spec, const void* mag, const void* mixture, int64_t mix_stride, int n_src) = 0;
   // AGLA: the momentum-free projection, then the extrapolation of three signals on the signal state (kernels_agla.h)
-  virtual int agla_init(const void* init_spec, const void* mag, double alpha, double beta, double gamma) = 0;
+  // (a schedule: iteration n takes entry min(n, n_sched) - 1 of the three host arrays)
+  virtual int agla_init_sched(const void* init_spec, const void* mag, int n_sched, const double* alpha, const double* beta,
+                              const double* gamma) = 0;
   virtual int iterate(int n_iter, bool eval_last, double sums[4]) = 0;
   // evaluations whose result cannot influence the run (tol == 0, no callback) stay on the device and are
   // read back once at the end: deferred_slot >= 0 makes iterate() park its sums in that slot
@@ -73,6 +75,13 @@ struct PlanBase {
   // MISI's backward sweep (kernels_misi_adjoint.h): the coupling step's adjoint, and one whole unfolded iteration's; stateless
   virtual int misi_mix_adjoint(int n_src, void* g, void* gmix) = 0;
   virtual int misi_step_adjoint(int n_src, const void* x_prev, const void* mag_fm, void* g, void* gmix, void* gmag_fm) = 0;
+  // AGLA's backward sweep (kernels_agla_adjoint.h): the extrapolation's adjoint alone, with the projection's, the closing step;
+  // stateless
+  virtual int agla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
+                                  void* gd, void* c_prev, void* dots_dev) = 0;
+  virtual int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
+                                void* gd, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) = 0;
+  virtual int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) = 0;
 
   virtual int rtisi_run(const void* mag, int look_ahead, int asym, int max_iter, double alpha, void* x_out) = 0;
   virtual int rtisi_record_elems(int look_ahead, int max_iter, int64_t* out) = 0;

@@ -19,6 +19,7 @@
 #include "kernels_misi.h"
 #include "kernels_agla.h"
 #include "kernels_misi_adjoint.h"
+#include "kernels_agla_adjoint.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
 #include "plan.h"
@@ -101,8 +102,12 @@ struct PlanT final : PlanBase {
   DevBuf misi_mix;                      // MISI: the mixtures, (batch / misi_k, length)
   int misi_k = 0;                       // ... and the sources per mixture
   DevBuf agla_t, agla_d;                // AGLA: t_n and (gamma != 1 only) d_n, (batch, length) each
-  T agla_alpha = 0, agla_beta = 0, agla_gamma = 1, agla_omg = 0;   // ... alpha, beta, gamma, 1 - gamma, rounded once
-  bool agla_general = false;            // ... gamma != 1: d exists
+  struct AglaCoef {
+    T alpha, beta, gamma, omg;          // ... alpha, beta, gamma, 1 - gamma, rounded once
+  };
+  std::vector<AglaCoef> agla_sched;     // ... iteration n takes entry min(n, size) - 1
+  bool agla_general = false;            // ... some gamma != 1: d exists
+  DevBuf agla_adj_part;                 // agla_*_adjoint: the workgroups' partial inner products
   int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
   FastState<T> fast;
   int tf_kind = -1, tf_mels = 0;
@@ -726,20 +731,23 @@ struct PlanT final : PlanBase {
   // AGLA (Peer, Welker & Gerkmann 2022; gamma = 1: the Fast Griffin-Lim of Perraudin, Balazs & Soendergaard 2013):
   //   y = P(c_{n-1}) ; t_n = (1 - gamma) d_{n-1} + gamma y ; c_n = t_n + alpha (t_n - t_{n-1}) ; d_n = t_n + beta (t_n - t_{n-1})
   // with P the momentum-free projection launch and c, t, d signals: c lives where the next launch reads it, t and d here
-  int agla_init(const void* init_spec, const void* magp, double alpha, double beta, double gamma) override {
-    SI_CHECK(alpha >= 0 && beta >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha, beta);
-    SI_CHECK(gamma > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma);
+  int agla_init_sched(const void* init_spec, const void* magp, int n_sched, const double* alpha, const double* beta,
+                      const double* gamma) override {
+    SI_CHECK(n_sched >= 1 && alpha && beta && gamma, SPECINV_EINVAL, "agla schedule: n_sched < 1 or a NULL array");
+    for (int i = 0; i < n_sched; ++i) {
+      SI_CHECK(alpha[i] >= 0 && beta[i] >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha[i], beta[i]);
+      SI_CHECK(gamma[i] > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma[i]);
+    }
     method = Method::None;
     coef = T(0);
     SI_TRY(init_common(init_spec, magp, fast::MODE_GLA, true));
-    agla_general = gamma != 1.0;
+    agla_general = false;
+    for (int i = 0; i < n_sched; ++i) agla_general = agla_general || gamma[i] != 1.0;
     SI_TRY(agla_t.reserve((size_t)B() * length * sizeof(T)));
     if (agla_general) SI_TRY(agla_d.reserve((size_t)B() * length * sizeof(T)));
     else agla_d.release();
-    agla_alpha = (T)alpha;
-    agla_beta = (T)beta;
-    agla_gamma = (T)gamma;
-    agla_omg = (T)(1.0 - gamma);
+    agla_sched.resize(n_sched);
+    for (int i = 0; i < n_sched; ++i) agla_sched[i] = AglaCoef{(T)alpha[i], (T)beta[i], (T)gamma[i], (T)(1.0 - gamma[i])};
     agla_n = 0;
     method = Method::Agla;
     return SPECINV_OK;
@@ -763,10 +771,11 @@ struct PlanT final : PlanBase {
     }
     a.t = agla_t.as<T>();
     a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
-    a.alpha = agla_alpha;
-    a.beta = agla_beta;
-    a.gamma = agla_gamma;
-    a.one_minus_gamma = agla_omg;
+    const AglaCoef& k = agla_sched[(size_t)std::min<int64_t>(agla_n, (int64_t)agla_sched.size() - 1)];   // iteration agla_n + 1
+    a.alpha = k.alpha;
+    a.beta = k.beta;
+    a.gamma = k.gamma;
+    a.one_minus_gamma = k.omg;
     a.L = length;
     a.first = agla_n == 0 ? 1 : 0;
     SI_TRY(agla_step_launch<T>(a, B(), stream));
@@ -1086,9 +1095,6 @@ struct PlanT final : PlanBase {
     SI_CHECK(x_prev && mag_fm && g && gmix && gmag_fm, SPECINV_EINVAL, "null pointer");
     SI_CHECK(n_src >= 1, SPECINV_EINVAL, "n_src must be >= 1, got %d", n_src);
     SI_CHECK(B() % n_src == 0, SPECINV_EINVAL, "the plan's batch (%d) is not a multiple of n_src (%d)", B(), n_src);
-    const int64_t ns = nspec();
-    SI_TRY(tmp_spec.reserve(ns * sizeof(C)));
-    SI_TRY(tmp_spec2.reserve(ns * sizeof(C)));
     MisiMixAdjArgs<T> a{};
     a.g = static_cast<T*>(g);
     a.gmix = static_cast<T*>(gmix);
@@ -1096,20 +1102,81 @@ struct PlanT final : PlanBase {
     a.L = length;
     a.K = n_src;
     SI_TRY(misi_mix_adjoint_launch<T>(a, B() / n_src, stream));                                       // u = M^T g / env
-    SI_TRY(stft_internal(a.g, length, tmp_spec.as<C>(), SPECINV_PAD_CONSTANT, T(1)));                // Y
-    SI_TRY(stft_internal(static_cast<const T*>(x_prev), length, tmp_spec2.as<C>()));                 // R
+    return proj_adjoint_stages(a.g, static_cast<const T*>(x_prev), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
+  }
+
+  // Stages 2-4 of a projection's adjoint (kernels_misi_adjoint.h), shared by MISI's sweep and AGLA's: u (batch, length), a signal
+  // cotangent already divided by the envelope, becomes A^T proj^T[x_prev, m] of its unscaled transform; gm is accumulated.
+  int proj_adjoint_stages(T* u, const T* x_prev, const T* mag_fm, T* gmag_fm) {
+    const int64_t ns = nspec();
+    SI_TRY(tmp_spec.reserve(ns * sizeof(C)));
+    SI_TRY(tmp_spec2.reserve(ns * sizeof(C)));
+    SI_TRY(stft_internal(u, length, tmp_spec.as<C>(), SPECINV_PAD_CONSTANT, T(1)));                  // Y
+    SI_TRY(stft_internal(x_prev, length, tmp_spec2.as<C>()));                                        // R
     MisiProjAdjArgs<T> p{};
     p.y = tmp_spec.as<C>();
     p.r = tmp_spec2.as<C>();
-    p.m = static_cast<const T*>(mag_fm);
-    p.gm = static_cast<T*>(gmag_fm);
+    p.m = mag_fm;
+    p.gm = gmag_fm;
     p.total = ns;
     p.F = n_freq;
     p.n_fft = N();
     p.onesided = cfg.onesided;
     p.inv_scale = fc.inv_scale;
     SI_TRY(misi_proj_adjoint_launch<T>(p, stream));                                                  // gR, halved; gm
-    return grad_from_spec(tmp_spec.as<C>(), a.g, fc.fwd_scale, length);                              // A^T
+    return grad_from_spec(tmp_spec.as<C>(), u, fc.fwd_scale, length);                                // A^T
+  }
+
+  // The adjoint of AGLA's extrapolation step n >= 2 (kernels_agla_adjoint.h); coef = {alpha_n, beta_n, gamma_n, alpha_{n-1},
+  // beta_{n-1}}, each rounded to T once.  Only agla_adj_part is written beside the caller's arrays.
+  int agla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc, void* gd,
+                          void* c_prev, void* dots_dev) override {
+    SI_CHECK(t_n && t_nm1 && coef && a && gc && c_prev && dots_dev, SPECINV_EINVAL, "null pointer");
+    SI_CHECK(coef[0] >= 0 && coef[1] >= 0 && coef[3] >= 0 && coef[4] >= 0 && coef[2] > 0, SPECINV_EINVAL,
+             "alpha and beta must be >= 0, gamma > 0");
+    SI_CHECK(gd != nullptr || coef[2] == 1.0, SPECINV_EINVAL, "gamma = %g needs gd", coef[2]);
+    SI_TRY(agla_adj_part.reserve((size_t)3 * kAglaAdjMaxGrid * sizeof(double)));
+    AglaAdjArgs<T> p{};
+    p.a = static_cast<T*>(a);
+    p.gc = static_cast<T*>(gc);
+    p.gd = static_cast<T*>(gd);
+    p.tn = static_cast<const T*>(t_n);
+    p.tp = static_cast<const T*>(t_nm1);
+    p.tpp = static_cast<const T*>(t_nm2);
+    p.env = env.as<T>();
+    p.c_prev = static_cast<T*>(c_prev);
+    p.partials = agla_adj_part.as<double>();
+    p.alpha = (T)coef[0];
+    p.beta = (T)coef[1];
+    p.gamma = (T)coef[2];
+    p.one_minus_gamma = (T)(1.0 - coef[2]);
+    p.alpha_p = (T)coef[3];
+    p.beta_p = (T)coef[4];
+    p.L = length;
+    return agla_step_adjoint_launch<T>(p, B(), static_cast<double*>(dots_dev), stream);
+  }
+
+  // ... followed by the adjoint of the projection y = P(c_{n-1}): gc becomes the cotangent of c_{n-1}
+  int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc, void* gd,
+                        void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) override {
+    SI_CHECK(mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
+    SI_TRY(agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots_dev));
+    return proj_adjoint_stages(static_cast<T*>(gc), static_cast<const T*>(c_prev), static_cast<const T*>(mag_fm),
+                               static_cast<T*>(gmag_fm));
+  }
+
+  // The closing step t_1 = c_1 = d_1 = P(c_0): gc <- (a + gc + gd) / env, then the projection's adjoint at c_0
+  int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) override {
+    SI_CHECK(c0 && a && gc && mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
+    AglaAdjArgs<T> p{};
+    p.a = const_cast<T*>(static_cast<const T*>(a));
+    p.gc = static_cast<T*>(gc);
+    p.gd = const_cast<T*>(static_cast<const T*>(gd));
+    p.env = env.as<T>();
+    p.L = length;
+    p.first = 1;
+    SI_TRY(agla_step_adjoint_launch<T>(p, B(), nullptr, stream));
+    return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
   }
 
   // RTISI-LA stages its target and its committed frames in the buffers that hold the target / frame scratch of a

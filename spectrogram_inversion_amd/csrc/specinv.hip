@@ -320,12 +320,20 @@ int specinv_misi_run(specinv_plan* plan, int max_iter, int eva_iter, double tol,
   return plan->impl->run_loop(max_iter, eva_iter, tol, metric, evals_out, n_evals_out, iters_done_out, cb, user);
 }
 
-int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma) {
-  // (the argument errors before the device is touched; PlanT::agla_init repeats them for its own callers)
-  SI_CHECK(alpha >= 0 && beta >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha, beta);
-  SI_CHECK(gamma > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma);
+int specinv_agla_init_sched(specinv_plan* plan, const void* init_spec, const void* mag, int n_sched, const double* alpha,
+                            const double* beta, const double* gamma) {
+  // (the argument errors before the device is touched; PlanT::agla_init_sched repeats them for its own callers)
+  SI_CHECK(n_sched >= 1, SPECINV_EINVAL, "n_sched must be >= 1, got %d", n_sched);
+  SI_CHECK(alpha && beta && gamma, SPECINV_EINVAL, "specinv_agla_init_sched: NULL %s", !alpha ? "alpha" : !beta ? "beta" : "gamma");
+  for (int i = 0; i < n_sched; ++i) {
+    SI_CHECK(alpha[i] >= 0 && beta[i] >= 0, SPECINV_EINVAL, "alpha and beta must be >= 0, got %g and %g", alpha[i], beta[i]);
+    SI_CHECK(gamma[i] > 0, SPECINV_EINVAL, "gamma must be > 0, got %g", gamma[i]);
+  }
   ENTER(plan);
-  return plan->impl->agla_init(init_spec, mag, alpha, beta, gamma);
+  return plan->impl->agla_init_sched(init_spec, mag, n_sched, alpha, beta, gamma);
+}
+int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma) {
+  return specinv_agla_init_sched(plan, init_spec, mag, 1, &alpha, &beta, &gamma);
 }
 int specinv_agla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   PLAN_OR_FAIL(plan);
@@ -408,6 +416,37 @@ int specinv_misi_step_adjoint(specinv_plan* plan, int n_src, const void* x_prev,
            plan->impl->cfg.batch, n_src);
   ENTER(plan);
   return plan->impl->misi_step_adjoint(n_src, x_prev, mag_fm, g_inout, gmix_accum, gmag_fm_accum);
+}
+// (the argument errors before the device is touched; PlanT repeats them for its own callers)
+#define AGLA_ADJ_ARGS(name)                                                                                                     \
+  SI_CHECK(t_n && t_nm1 && coef && a_inout && gc_inout && c_prev_out && dots_dev_out, SPECINV_EINVAL, name ": NULL %s",         \
+           !t_n ? "t_n" : !t_nm1 ? "t_nm1" : !coef ? "coef" : !a_inout ? "a_inout" : !gc_inout ? "gc_inout" : !c_prev_out ? "c_prev_out" \
+                                                                                                            : "dots_dev_out"); \
+  SI_CHECK(coef[0] >= 0 && coef[1] >= 0 && coef[3] >= 0 && coef[4] >= 0, SPECINV_EINVAL, name ": alpha and beta must be >= 0"); \
+  SI_CHECK(coef[2] > 0, SPECINV_EINVAL, name ": gamma must be > 0, got %g", coef[2]);                                           \
+  SI_CHECK(gd_inout != nullptr || coef[2] == 1.0, SPECINV_EINVAL, name ": gamma = %g needs gd_inout", coef[2])
+
+int specinv_agla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                                void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out) {
+  AGLA_ADJ_ARGS("specinv_agla_extrap_adjoint");
+  ENTER(plan);
+  return plan->impl->agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out);
+}
+int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                              void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out,
+                              const void* mag_fm, void* gmag_fm_accum) {
+  AGLA_ADJ_ARGS("specinv_agla_step_adjoint");
+  SI_CHECK(mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_agla_step_adjoint: NULL %s", mag_fm ? "gmag_fm_accum" : "mag_fm");
+  ENTER(plan);
+  return plan->impl->agla_step_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out, mag_fm,
+                                       gmag_fm_accum);
+}
+int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
+                               void* gmag_fm_accum) {
+  SI_CHECK(c0 && a && gc_inout && mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_agla_first_adjoint: NULL %s",
+           !c0 ? "c0" : !a ? "a" : !gc_inout ? "gc_inout" : !mag_fm ? "mag_fm" : "gmag_fm_accum");
+  ENTER(plan);
+  return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum);
 }
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum) {
   ENTER(plan);

@@ -290,6 +290,19 @@ class Plan:
                                               float(alpha), float(beta), float(gamma)))
         self._method = "agla"
 
+    def agla_init_sched(self, init_spec, mag, alpha, beta, gamma):
+        """`agla_init` with a schedule (`specinv_agla_init_sched`): `alpha`, `beta`, `gamma` are sequences of one length, iteration
+        n takes entry min(n, length) - 1."""
+        self._sync_stream()
+        n = len(alpha)
+        assert n >= 1 and len(beta) == n and len(gamma) == n, "alpha, beta and gamma must be non-empty and of one length"
+        spec = None if init_spec is None else self._in(init_spec, self.cdtype, self._spec_shape())
+        m = None if mag is None else self._in(mag, self.dtype, self._spec_shape())
+        arr = [(C.c_double * n)(*[float(v) for v in seq]) for seq in (alpha, beta, gamma)]
+        _lib.check(self.lib.specinv_agla_init_sched(self._h, None if spec is None else spec.data_ptr(),
+                                                    None if m is None else m.data_ptr(), n, *arr))
+        self._method = "agla"
+
     def agla_iterate(self, n_iter: int, eval_last: bool = False):
         """`n_iter` AGLA iterations (projection launch + extrapolation launch each); the evaluation sums of the last if asked."""
         self._sync_stream()
@@ -435,6 +448,47 @@ class Plan:
         mp = self._inout(gmix, (self._mix_rows(n_src) or gmix.shape[0], self.length), "gmix")
         _lib.check(self.lib.specinv_misi_step_adjoint(self._h, n_src, x_prev.data_ptr(), mag_fm.data_ptr(), gp, mp,
                                                       self._inout(gmag_fm, fm, "gmag_fm")))
+
+    def _agla_adjoint_args(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots):
+        sig = (self.batch, self.length)
+        t_n, t_nm1 = self._in(t_n, self.dtype, sig), self._in(t_nm1, self.dtype, sig)
+        t_nm2 = None if t_nm2 is None else self._in(t_nm2, self.dtype, sig)
+        assert len(coef) == 5, "coef is (alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1})"
+        assert dots.dtype == torch.float64 and dots.numel() == 3 and dots.is_contiguous() and dots.device == self.device, \
+            f"dots must be 3 contiguous float64 on {self.device}"
+        keep = (t_n, t_nm1, t_nm2)                                 # (converted copies stay alive until the call is enqueued)
+        return keep, (t_n.data_ptr(), t_nm1.data_ptr(), None if t_nm2 is None else t_nm2.data_ptr(),
+                      (C.c_double * 5)(*[float(v) for v in coef]), self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
+                      None if gd is None else self._inout(gd, sig, "gd"), self._inout(c_prev, sig, "c_prev"),
+                      C.c_void_p(dots.data_ptr()))
+
+    def agla_extrap_adjoint(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots):
+        """Adjoint of AGLA's extrapolation step n >= 2 (`specinv_agla_extrap_adjoint`), in place on the sweep's state `a`, `gc`,
+        `gd` (None: every gamma is 1), all (batch, length): `coef` = (alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1}),
+        `t_nm2` None for n = 2; `c_prev` receives c_{n-1}, `dots` (3 float64 on the device) the gradients of alpha_n, beta_n,
+        gamma_n."""
+        self._sync_stream()
+        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
+        _lib.check(self.lib.specinv_agla_extrap_adjoint(self._h, *ptrs))
+
+    def agla_step_adjoint(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots, mag_fm, gmag_fm):
+        """`agla_extrap_adjoint`, then the adjoint of the projection at `c_prev` (`specinv_agla_step_adjoint`): `gc` becomes the
+        cotangent of c_{n-1}, `gmag_fm` gains the magnitude's.  `mag_fm` and `gmag_fm` are frame-major, (batch, n_frames, n_freq)."""
+        self._sync_stream()
+        fm = (self.batch, self.n_frames, self.n_freq)
+        mag_fm = self._in(mag_fm, self.dtype, fm)
+        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
+        _lib.check(self.lib.specinv_agla_step_adjoint(self._h, *ptrs, mag_fm.data_ptr(), self._inout(gmag_fm, fm, "gmag_fm")))
+
+    def agla_first_adjoint(self, c0, a, gc, gd, mag_fm, gmag_fm):
+        """The closing step of AGLA's sweep (`specinv_agla_first_adjoint`): `gc` becomes the cotangent of `c0` = ISTFT(start) from
+        `a`, `gc` and `gd` (None: absent), the cotangents of t_1, c_1 and d_1; `gmag_fm` gains the magnitude's."""
+        self._sync_stream()
+        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
+        c0, mag_fm = self._in(c0, self.dtype, sig), self._in(mag_fm, self.dtype, fm)
+        _lib.check(self.lib.specinv_agla_first_adjoint(self._h, c0.data_ptr(), self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
+                                                       None if gd is None else self._inout(gd, sig, "gd"), mag_fm.data_ptr(),
+                                                       self._inout(gmag_fm, fm, "gmag_fm")))
 
     def rtisi(self, mag, look_ahead, asymmetric_window, max_iter, alpha) -> torch.Tensor:
         self._sync_stream()
