@@ -311,6 +311,17 @@ int specinv_mel_nnls_setup(specinv_plan* plan, const void* mel_fb, int n_mels, d
  * mel entries are valid.  EINVAL: n_iter < 0, power <= 0 or not finite, NULL pointers, no setup on this plan (all checked
  * before anything is enqueued); EUNSUPPORTED: a frame that does not fit a CU's LDS (beyond n_fft 8192 in float64). */
 int specinv_mel_nnls(specinv_plan* plan, const void* mel, int n_iter, double power, void* mag_out);
+/* The reverse sweep of specinv_mel_nnls (mel_to_stft_unfolded): gmag (B, F, T), the gradient of a loss with respect to mag_out,
+ * -> gmel_out (B, n_mels, T), its gradient with respect to mel, for the same mel, n_iter and power, in one launch on the plan's
+ * stream.  The launch recomputes the iteration from mel and keeps its active sets [s_k > 0] in LDS, one bit per bin and
+ * iteration, so nothing is recorded by the forward call.  d max(0, u) / du is 0 at u = 0 and the root's derivative 0 at s = 0:
+ * a silent frame and a band that touches no bin get exact zeros; n_iter = 0 gives zeros.  The filterbank is a constant.
+ * EINVAL: as specinv_mel_nnls, gmag / gmel_out NULL (all checked before anything is enqueued); EUNSUPPORTED: n_iter beyond
+ * specinv_mel_nnls_adjoint_max_iter (the message states the limit). */
+int specinv_mel_nnls_adjoint(specinv_plan* plan, const void* mel, int n_iter, double power, const void* gmag, void* gmel_out);
+/* *out = the largest n_iter specinv_mel_nnls_adjoint admits on this plan with its filterbank: what a CU's LDS holds beside one
+ * frame.  EINVAL: out NULL, no setup on this plan; EUNSUPPORTED: the frame alone does not fit. */
+int specinv_mel_nnls_adjoint_max_iter(specinv_plan* plan, int* out);
 
 /* ---- L_BFGS building blocks (methods.py:509-569 + torch.optim.LBFGS) -------------------- */
 /* transform kinds for the fused forward/backward: V = |STFT(x)| or V = log1p(M |STFT(x)|) */

@@ -135,6 +135,8 @@ SIGNATURES = {
     "specinv_read_doubles": (C.c_int, [_P, _P, C.c_int, _DP]),
     "specinv_mel_nnls_setup": (C.c_int, [_P, _P, C.c_int, _D]),
     "specinv_mel_nnls": (C.c_int, [_P, _P, C.c_int, _D, _P]),
+    "specinv_mel_nnls_adjoint": (C.c_int, [_P, _P, C.c_int, _D, _P, _P]),
+    "specinv_mel_nnls_adjoint_max_iter": (C.c_int, [_P, _IP]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "kernels_mel_nnls.h"
+#include "kernels_mel_nnls_adjoint.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -503,6 +504,23 @@ int specinv_mel_nnls(specinv_plan* plan, const void* mel, int n_iter, double pow
   SI_CHECK(plan->impl->mel_nnls != nullptr, SPECINV_EINVAL, "mel_nnls: specinv_mel_nnls_setup has not been called on this plan");
   ENTER(plan);
   return mel_nnls_run(*plan->impl, mel, n_iter, power, mag_out);
+}
+int specinv_mel_nnls_adjoint(specinv_plan* plan, const void* mel, int n_iter, double power, const void* gmag, void* gmel_out) {
+  SI_CHECK(n_iter >= 0, SPECINV_EINVAL, "mel_nnls_adjoint: n_iter must be >= 0 (got %d)", n_iter);
+  SI_CHECK(std::isfinite(power) && power > 0, SPECINV_EINVAL, "mel_nnls_adjoint: power must be finite and > 0 (got %g)", power);
+  SI_CHECK(mel != nullptr && gmag != nullptr && gmel_out != nullptr, SPECINV_EINVAL, "mel_nnls_adjoint: mel / gmag / gmel_out is NULL");
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->mel_nnls != nullptr, SPECINV_EINVAL,
+           "mel_nnls_adjoint: specinv_mel_nnls_setup has not been called on this plan");
+  ENTER(plan);
+  return mel_nnls_adjoint_run(*plan->impl, mel, n_iter, power, gmag, gmel_out);
+}
+int specinv_mel_nnls_adjoint_max_iter(specinv_plan* plan, int* out) {
+  SI_CHECK(out != nullptr, SPECINV_EINVAL, "mel_nnls_adjoint_max_iter: out is NULL");
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->mel_nnls != nullptr, SPECINV_EINVAL,
+           "mel_nnls_adjoint_max_iter: specinv_mel_nnls_setup has not been called on this plan");
+  return mel_nnls_adjoint_max_iter(*plan->impl, out);
 }
 
 int specinv_transform_setup(specinv_plan* plan, int kind, const void* mel_fb, int n_mels) {
