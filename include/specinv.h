@@ -266,6 +266,22 @@ int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t
  * to the start. */
 int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
                                void* gmag_fm_accum);
+/* ---- one projection as a layer (gla_projection; csrc/kernels_proj_adjoint.h) ---------------
+ * y = P(x; m) = ISTFT(m S / (|S| + 1e-16)), S = STFT(x): one Griffin-Lim iteration without momentum (methods.py:241-248), on
+ * signals.  x and y_out are (batch, length), mag_fm is frame-major, (batch, n_frames, n_freq); y_out must not alias x.  All three
+ * entries are stateless as the MISI / AGLA adjoint entries above: a plan in any method state, scratch only.  SPECINV_EINVAL before
+ * anything is enqueued: a NULL pointer, an aliased output. */
+int specinv_project(specinv_plan* plan, const void* x, const void* mag_fm, void* y_out);
+/* its adjoint at (x, mag_fm): g_y (batch, length), the cotangent of y, is read and left as it is; g_x_out (batch, length) and
+ * gmag_fm_out (batch, n_frames, n_freq) are written in full, not accumulated.  S is recomputed from x.  Where |S| = 0 the second
+ * term of the projection's derivative is 0 (k_misi_proj_adjoint's convention).  No atomics: two calls give the same bits. */
+int specinv_project_adjoint(specinv_plan* plan, const void* x, const void* mag_fm, const void* g_y, void* g_x_out,
+                            void* gmag_fm_out);
+/* How specinv_project_adjoint runs on this plan (diagnostics; the tests assert which path they exercised): *kind_out = 0 the
+ * staged path (two transforms, the element-wise adjoint, the inverse transform, every spectrum through device memory: any
+ * configuration), 1 one fused launch that keeps a frame's spectra on the chip (one-sided, n_fft 128 / 256 / 512 / 1024 / 2048,
+ * float32 and float64; SPECINV_PROJ_ADJ_FUSED=0 in the environment when the plan is created selects 0 instead). */
+int specinv_project_adjoint_kind(const specinv_plan* plan, int32_t* kind_out);
 /* adjoint of specinv_phase_init: gmag += d/dmag of <g_spec, phase_init(mag)> */
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum);
 

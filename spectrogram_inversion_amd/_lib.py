@@ -101,6 +101,9 @@ SIGNATURES = {
     "specinv_agla_extrap_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P]),
     "specinv_agla_step_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P, _P, _P]),
     "specinv_agla_first_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "specinv_project": (C.c_int, [_P, _P, _P, _P]),
+    "specinv_project_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "specinv_project_adjoint_kind": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "specinv_rtisi_run": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P]),
     "specinv_rtisi_record_elems": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "specinv_rtisi_run_recorded": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _D, _P, _P]),

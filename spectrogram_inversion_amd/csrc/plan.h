@@ -82,6 +82,11 @@ struct PlanBase {
   virtual int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
                                 void* gd, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) = 0;
   virtual int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) = 0;
+  // gla_projection: y = ISTFT(m S / (|S| + 1e-16)), S = STFT(x), and its adjoint - one fused launch where
+  // project_adjoint_kind() is 1, else the stages of the sweeps above; stateless
+  virtual int project(const void* x, const void* mag_fm, void* y_out) = 0;
+  virtual int project_adjoint(const void* x, const void* mag_fm, const void* g_y, void* g_x_out, void* gmag_fm_out) = 0;
+  virtual int project_adjoint_kind() const = 0;
 
   virtual int rtisi_run(const void* mag, int look_ahead, int asym, int max_iter, double alpha, void* x_out) = 0;
   virtual int rtisi_record_elems(int look_ahead, int max_iter, int64_t* out) = 0;

@@ -20,6 +20,7 @@
 #include "kernels_agla.h"
 #include "kernels_misi_adjoint.h"
 #include "kernels_agla_adjoint.h"
+#include "proj_adjoint_api.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
 #include "plan.h"
@@ -109,6 +110,8 @@ struct PlanT final : PlanBase {
   bool agla_general = false;            // ... some gamma != 1: d exists
   DevBuf agla_adj_part;                 // agla_*_adjoint: the workgroups' partial inner products
   int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
+  bool proj_adj_fused = false;          // project_adjoint: k_wave_proj_adjoint (kernels_proj_adjoint.h) instead of the stages
+  int proj_adj_max_waves = 0;           // ... SPECINV_PROJ_ADJ_WAVES: at most so many waves per launch (0: the chip's fill)
   FastState<T> fast;
   int tf_kind = -1, tf_mels = 0;
 
@@ -333,6 +336,15 @@ struct PlanT final : PlanBase {
       const void* fns[] = {(const void*)k_big_rows<T, false, false>, (const void*)k_big_rows<T, false, true>,
                            (const void*)k_big_rows<T, true, false>, (const void*)k_big_rows<T, true, true>};
       for (const void* fn : fns) SI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds_bytes, 64 * 1024)));
+    }
+    // gla_projection's backward pass in one launch: one-sided n_fft 128 ... 2048, both dtypes (measured: DESIGN 3.16).
+    // SPECINV_PROJ_ADJ_FUSED=0 keeps the stages, SPECINV_PROJ_ADJ_WAVES=k caps the launch (experiments / tests).
+    {
+      const char* fe = getenv("SPECINV_PROJ_ADJ_FUSED");
+      const char* we = getenv("SPECINV_PROJ_ADJ_WAVES");
+      proj_adj_fused = cfg.onesided && proj_adjoint_covers(n, (int)sizeof(T)) && wave_iter_fits(n, cfg.n_frames, cfg.batch, false) &&
+                       !(fe && fe[0] == '0');
+      proj_adj_max_waves = we ? std::max(0, atoi(we)) : 0;
     }
     SI_TRY(sums.reserve(16 * sizeof(double)));
     SI_TRY(fast.setup(cfg, h_window, length, pad));
@@ -1177,6 +1189,48 @@ struct PlanT final : PlanBase {
     p.first = 1;
     SI_TRY(agla_step_adjoint_launch<T>(p, B(), nullptr, stream));
     return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
+  }
+
+  // gla_projection's forward pass: the transform, the projection in the internal layout, the inverse transform.  Only scratch is
+  // written (tmp_spec, the frames of istft_internal).
+  int project(const void* xin, const void* mag_fm, void* y_out) override {
+    SI_CHECK(xin && mag_fm && y_out && y_out != xin, SPECINV_EINVAL, "null or aliased pointer");
+    const int64_t ns = nspec();
+    SI_TRY(tmp_spec.reserve(ns * sizeof(C)));
+    SI_TRY(stft_internal(static_cast<const T*>(xin), length, tmp_spec.as<C>()));
+    SI_TRY(project_launch<T>(tmp_spec.as<C>(), static_cast<const T*>(mag_fm), ns, stream));
+    return istft_internal(tmp_spec.as<C>(), static_cast<T*>(y_out));
+  }
+
+  int project_adjoint_kind() const override { return proj_adj_fused ? 1 : 0; }
+
+  // ... and its adjoint: g_x_out and gmag_fm_out are written in full, g_y is only read.  Fused: k_wave_proj_adjoint leaves the frames
+  // of A^T gR, launch_grad_fold overlap-adds them.  Staged: u = g_y / env into g_x_out, then proj_adjoint_stages in place on it with a
+  // zeroed magnitude cotangent.  Only scratch is written (frames; tmp_spec, tmp_spec2).
+  int project_adjoint(const void* xin, const void* mag_fm, const void* g_y, void* g_x_out, void* gmag_fm_out) override {
+    SI_CHECK(xin && mag_fm && g_y && g_x_out && gmag_fm_out && g_x_out != g_y && g_x_out != xin, SPECINV_EINVAL, "null or aliased pointer");
+    if (proj_adj_fused) {
+      SI_TRY(frames_needed());
+      ProjAdjArgs<T> p{};
+      p.c = frame_cfg(length);
+      p.x = static_cast<const T*>(xin);
+      p.g = static_cast<const T*>(g_y);
+      p.env = env.as<T>();
+      p.mag = static_cast<const T*>(mag_fm);
+      p.gmag = static_cast<T*>(gmag_fm_out);
+      p.frames = frames.template as<T>();
+      p.batch = B();
+      p.max_waves = proj_adj_max_waves;
+      SI_TRY(proj_adjoint_launch<T>(p, stream));
+      return launch_grad_fold(frames.template as<T>(), static_cast<T*>(g_x_out), length);
+    }
+    const int64_t total = (int64_t)B() * length;
+    hipLaunchKernelGGL((k_div_env<T>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, static_cast<const T*>(g_y),
+                       env.as<T>(), static_cast<T*>(g_x_out), length, total);
+    SI_HIP(hipGetLastError());
+    SI_HIP(hipMemsetAsync(gmag_fm_out, 0, nspec() * sizeof(T), stream));
+    return proj_adjoint_stages(static_cast<T*>(g_x_out), static_cast<const T*>(xin), static_cast<const T*>(mag_fm),
+                               static_cast<T*>(gmag_fm_out));
   }
 
   // RTISI-LA stages its target and its committed frames in the buffers that hold the target / frame scratch of a

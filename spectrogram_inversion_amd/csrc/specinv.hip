@@ -449,6 +449,24 @@ int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a
   ENTER(plan);
   return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum);
 }
+int specinv_project(specinv_plan* plan, const void* x, const void* mag_fm, void* y_out) {
+  SI_CHECK(x && mag_fm && y_out, SPECINV_EINVAL, "specinv_project: NULL %s", !x ? "x" : !mag_fm ? "mag_fm" : "y_out");
+  SI_CHECK(y_out != x, SPECINV_EINVAL, "specinv_project: y_out must not alias x");
+  ENTER(plan);
+  return plan->impl->project(x, mag_fm, y_out);
+}
+int specinv_project_adjoint(specinv_plan* plan, const void* x, const void* mag_fm, const void* g_y, void* g_x_out, void* gmag_fm_out) {
+  SI_CHECK(x && mag_fm && g_y && g_x_out && gmag_fm_out, SPECINV_EINVAL, "specinv_project_adjoint: NULL %s",
+           !x ? "x" : !mag_fm ? "mag_fm" : !g_y ? "g_y" : !g_x_out ? "g_x_out" : "gmag_fm_out");
+  SI_CHECK(g_x_out != g_y && g_x_out != x, SPECINV_EINVAL, "specinv_project_adjoint: g_x_out must not alias g_y or x");
+  ENTER(plan);
+  return plan->impl->project_adjoint(x, mag_fm, g_y, g_x_out, gmag_fm_out);
+}
+int specinv_project_adjoint_kind(const specinv_plan* plan, int32_t* kind_out) {
+  SI_CHECK(plan != nullptr && plan->impl && kind_out, SPECINV_EINVAL, "null argument");
+  *kind_out = plan->impl->project_adjoint_kind();
+  return SPECINV_OK;
+}
 int specinv_phase_init_adjoint(specinv_plan* plan, const void* mag, const void* g_spec, void* gmag_accum) {
   ENTER(plan);
   return plan->impl->phase_init_adjoint(mag, g_spec, gmag_accum);

@@ -490,6 +490,36 @@ class Plan:
                                                        None if gd is None else self._inout(gd, sig, "gd"), mag_fm.data_ptr(),
                                                        self._inout(gmag_fm, fm, "gmag_fm")))
 
+    @property
+    def project_adjoint_kind(self) -> str:
+        """How `project_adjoint` runs on this plan (`specinv_project_adjoint_kind`): "staged" - two transforms, the element-wise
+        adjoint and the inverse transform, every spectrum through device memory - or one "fused" launch."""
+        kind = C.c_int32(-1)
+        _lib.check(self.lib.specinv_project_adjoint_kind(self._h, C.byref(kind)))
+        return ("staged", "fused")[kind.value]
+
+    def project(self, x, mag_fm):
+        """y = ISTFT(mag S / (|S| + 1e-16)), S = STFT(x) (`specinv_project`): `x` (batch, length), `mag_fm` frame-major,
+        (batch, n_frames, n_freq).  Stateless: a running method is not disturbed."""
+        self._sync_stream()
+        x = self._in(x, self.dtype, (self.batch, self.length))
+        mag_fm = self._in(mag_fm, self.dtype, (self.batch, self.n_frames, self.n_freq))
+        out = torch.empty((self.batch, self.length), dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.specinv_project(self._h, x.data_ptr(), mag_fm.data_ptr(), out.data_ptr()))
+        return out
+
+    def project_adjoint(self, x, mag_fm, g_y):
+        """The adjoint of `project` at (`x`, `mag_fm`) applied to `g_y` (batch, length) (`specinv_project_adjoint`): the cotangents
+        of `x` and of `mag_fm`, both new tensors written in full; `g_y` is left as it is."""
+        self._sync_stream()
+        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
+        x, mag_fm, g_y = self._in(x, self.dtype, sig), self._in(mag_fm, self.dtype, fm), self._in(g_y, self.dtype, sig)
+        g_x = torch.empty(sig, dtype=self.dtype, device=self.device)
+        g_mag = torch.empty(fm, dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.specinv_project_adjoint(self._h, x.data_ptr(), mag_fm.data_ptr(), g_y.data_ptr(), g_x.data_ptr(),
+                                                    g_mag.data_ptr()))
+        return g_x, g_mag
+
     def rtisi(self, mag, look_ahead, asymmetric_window, max_iter, alpha) -> torch.Tensor:
         self._sync_stream()
         mag = self._in(mag, self.dtype, self._spec_shape())
