@@ -195,6 +195,17 @@ int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag
  * a NULL array, an alpha or beta entry < 0, a gamma entry <= 0, a NULL plan. */
 int specinv_agla_init_sched(specinv_plan* plan, const void* init_spec, const void* mag, int n_sched, const double* alpha,
                             const double* beta, const double* gamma);
+/* Known bins and known samples for the iterations that follow (constrained_griffin_lim; csrc/kernels_cgla.h).  With M the mask of
+ * known bins and K their values, the host layer passes mag = where(M, 0, m) to specinv_agla_init and here
+ *     offset = where(W, xk, ISTFT(where(M, K, 0))),  (batch, length) in the plan's dtype,
+ *     fixed_mask = W, (batch, length) uint8, non-zero where the sample xk is known - or NULL: no sample is.
+ * Both are device arrays; the plan keeps copies (device_bytes grows by batch * length * (sizeof(T) [+ 1])).  Every iteration then
+ * runs k_cgla_step for k_agla_step:  u = y + offset;  t_n = where(W, offset, (1 - gamma) d_{n-1} + gamma u);  c_n and d_n as above;
+ * t, c and d hold xk bit for bit under W.  Both NULL clears the constraint, and so does every specinv_*_init.  An evaluating
+ * iteration's sums compare against mag, zeros under M: evaluate |STFT(t_n)| against the full target instead (specinv_stft,
+ * specinv_metric_sums).  SPECINV_ESTATE: the plan is not in the AGLA state (call after specinv_agla_init / _init_sched).
+ * SPECINV_EINVAL, before anything is enqueued: a NULL offset with a fixed_mask, a NULL plan. */
+int specinv_agla_constrain(specinv_plan* plan, const void* offset, const void* fixed_mask);
 /* n_iter times: one projection launch, one extrapolation launch (k_agla_step).  An evaluating iteration's sums compare
  * |STFT(c_{n-1})|, the signal that entered the projection, against the target.  SPECINV_ESTATE before specinv_agla_init;
  * specinv_gla_iterate / _run, specinv_admm_iterate / _run and specinv_misi_iterate / _run return SPECINV_ESTATE on a plan in

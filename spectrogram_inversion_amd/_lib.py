@@ -85,6 +85,7 @@ SIGNATURES = {
     "specinv_misi_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
     "specinv_agla_init": (C.c_int, [_P, _P, _P, _D, _D, _D]),
     "specinv_agla_init_sched": (C.c_int, [_P, _P, _P, C.c_int, _DP, _DP, _DP]),
+    "specinv_agla_constrain": (C.c_int, [_P, _P, _P]),
     "specinv_agla_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),
     "specinv_agla_run": (C.c_int, [_P, C.c_int, C.c_int, _D, C.c_int, C.POINTER(Eval), _IP, _IP, EVAL_CB, _P]),
     "specinv_get_wave": (C.c_int, [_P, _P]),

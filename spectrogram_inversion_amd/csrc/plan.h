@@ -50,6 +50,8 @@ struct PlanBase {
   // (a schedule: iteration n takes entry min(n, n_sched) - 1 of the three host arrays)
   virtual int agla_init_sched(const void* init_spec, const void* mag, int n_sched, const double* alpha, const double* beta,
                               const double* gamma) = 0;
+  // ... under known bins and known samples for the iterations that follow (kernels_cgla.h); both nullptr: no constraint
+  virtual int agla_constrain(const void* offset, const void* fixed_mask) = 0;
   virtual int iterate(int n_iter, bool eval_last, double sums[4]) = 0;
   // evaluations whose result cannot influence the run (tol == 0, no callback) stay on the device and are
   // read back once at the end: deferred_slot >= 0 makes iterate() park its sums in that slot

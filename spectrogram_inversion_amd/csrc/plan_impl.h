@@ -20,6 +20,7 @@
 #include "kernels_agla.h"
 #include "kernels_misi_adjoint.h"
 #include "kernels_agla_adjoint.h"
+#include "kernels_cgla.h"
 #include "proj_adjoint_api.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
@@ -110,6 +111,7 @@ struct PlanT final : PlanBase {
   bool agla_general = false;            // ... some gamma != 1: d exists
   DevBuf agla_adj_part;                 // agla_*_adjoint: the workgroups' partial inner products
   int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
+  DevBuf cgla_off, cgla_mask;           // agla_constrain: where(W, xk, k) and W, (batch, length) each (kernels_cgla.h); no p: none set
   bool proj_adj_fused = false;          // project_adjoint: k_wave_proj_adjoint (kernels_proj_adjoint.h) instead of the stages
   int proj_adj_max_waves = 0;           // ... SPECINV_PROJ_ADJ_WAVES: at most so many waves per launch (0: the chip's fill)
   FastState<T> fast;
@@ -630,6 +632,8 @@ struct PlanT final : PlanBase {
     const int64_t ns = nspec();
     count = (double)ns;
     const C* start_user = static_cast<const C*>(init_spec);
+    cgla_off.release();                   // a constraint (agla_constrain) belongs to the run it was set on
+    cgla_mask.release();
     keep_latched = keep_state;
     fast.keep_state = keep_state;
     fast.plain_state = plain_state;
@@ -716,11 +720,11 @@ struct PlanT final : PlanBase {
     return launch_mix();
   }
 
-  // The coupling step on the state the next projection launch reads: the plan's x on the coverage kernels (after the overlap-add,
-  // after the swap of the register / ring form); xb[cur] on the float32 wave-level kernels, whose fused forms keep the chunk
-  // tails beside it - the sum takes them in, the correction goes to xb[cur], and xb + tail is again what the launch loads.
-  int launch_mix() {
-    MisiMixArgs<T> a{};
+  // The state the next projection launch reads, for a kernel that edits it between two launches (MisiMixArgs, AglaStepArgs,
+  // CglaStepArgs): the plan's x on the coverage kernels (after the overlap-add, after the swap of the register / ring form);
+  // xb[cur] on the float32 wave-level kernels, whose fused forms keep the chunk tails beside it.
+  template <typename Args>
+  void signal_state(Args& a) {
     a.x = x.as<T>();
     if (fast_path()) {
       a.x = fast.state_rows();
@@ -734,6 +738,13 @@ struct PlanT final : PlanBase {
         a.pb = fast.OV / 2;
       }
     }
+  }
+
+  // The coupling step on that state: the sum takes the tails in, the correction goes to xb[cur], and xb + tail is again what the
+  // launch loads.
+  int launch_mix() {
+    MisiMixArgs<T> a{};
+    signal_state(a);
     a.mix = misi_mix.as<T>();
     a.L = length;
     a.K = misi_k;
@@ -765,22 +776,33 @@ struct PlanT final : PlanBase {
     return SPECINV_OK;
   }
 
+  // Known bins and known samples for the iterations that follow (kernels_cgla.h): offset = where(W, xk, k) (batch, length) in the
+  // plan's dtype, fixed_mask = W as bytes or nullptr; both nullptr: none.  The plan keeps copies, as MISI keeps its mixture.
+  int agla_constrain(const void* offset, const void* fixed_mask) override {
+    SI_CHECK(method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");
+    SI_CHECK(offset || !fixed_mask, SPECINV_EINVAL, "agla_constrain: a fixed_mask needs an offset");
+    const size_t n = (size_t)B() * length;
+    if (!offset) {
+      cgla_off.release();
+      cgla_mask.release();
+      return SPECINV_OK;
+    }
+    SI_TRY(cgla_off.reserve(n * sizeof(T)));
+    SI_HIP(hipMemcpyAsync(cgla_off.p, offset, n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    if (fixed_mask) {
+      SI_TRY(cgla_mask.reserve(n));
+      SI_HIP(hipMemcpyAsync(cgla_mask.p, fixed_mask, n, hipMemcpyDeviceToDevice, stream));
+    } else {
+      cgla_mask.release();
+    }
+    return SPECINV_OK;
+  }
+
   // The extrapolation on the state the projection launch has just written and the next one reads (launch_mix's contract)
   int launch_agla() {
+    if (cgla_off.p != nullptr) return launch_cgla();
     AglaStepArgs<T> a{};
-    a.x = x.as<T>();
-    if (fast_path()) {
-      a.x = fast.state_rows();
-      a.tail = fast.state_tails();
-      if (a.tail != nullptr) {
-        a.n_frames = Tn();
-        a.nchunks = fast.nchunks;
-        a.skew = fast.skew;
-        a.hop = cfg.hop_length;
-        a.nb = fast.OV - 1;
-        a.pb = fast.OV / 2;
-      }
-    }
+    signal_state(a);
     a.t = agla_t.as<T>();
     a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
     const AglaCoef& k = agla_sched[(size_t)std::min<int64_t>(agla_n, (int64_t)agla_sched.size() - 1)];   // iteration agla_n + 1
@@ -791,6 +813,26 @@ struct PlanT final : PlanBase {
     a.L = length;
     a.first = agla_n == 0 ? 1 : 0;
     SI_TRY(agla_step_launch<T>(a, B(), stream));
+    ++agla_n;
+    return SPECINV_OK;
+  }
+
+  // ... under a constraint: k_cgla_step, the same contract with the offset and the mask read beside it
+  int launch_cgla() {
+    CglaStepArgs<T> a{};
+    signal_state(a);
+    a.t = agla_t.as<T>();
+    a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
+    a.offset = cgla_off.as<T>();
+    a.mask = cgla_mask.as<uint8_t>();
+    const AglaCoef& k = agla_sched[(size_t)std::min<int64_t>(agla_n, (int64_t)agla_sched.size() - 1)];   // iteration agla_n + 1
+    a.alpha = k.alpha;
+    a.beta = k.beta;
+    a.gamma = k.gamma;
+    a.one_minus_gamma = k.omg;
+    a.L = length;
+    a.first = agla_n == 0 ? 1 : 0;
+    SI_TRY(cgla_step_launch<T>(a, B(), stream));
     ++agla_n;
     return SPECINV_OK;
   }

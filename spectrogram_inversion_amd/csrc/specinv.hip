@@ -336,6 +336,13 @@ int specinv_agla_init_sched(specinv_plan* plan, const void* init_spec, const voi
 int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag, double alpha, double beta, double gamma) {
   return specinv_agla_init_sched(plan, init_spec, mag, 1, &alpha, &beta, &gamma);
 }
+int specinv_agla_constrain(specinv_plan* plan, const void* offset, const void* fixed_mask) {
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");
+  SI_CHECK(offset || !fixed_mask, SPECINV_EINVAL, "specinv_agla_constrain: a fixed_mask needs an offset");
+  ENTER(plan);
+  return plan->impl->agla_constrain(offset, fixed_mask);
+}
 int specinv_agla_iterate(specinv_plan* plan, int n_iter, int eval_last, double sums_host[4]) {
   PLAN_OR_FAIL(plan);
   SI_CHECK(plan->impl->method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");

@@ -303,6 +303,22 @@ class Plan:
                                                     None if m is None else m.data_ptr(), n, *arr))
         self._method = "agla"
 
+    def agla_constrain(self, offset, fixed_mask=None):
+        """Known bins and known samples for the AGLA iterations that follow (`specinv_agla_constrain`): `offset` (batch, length) in
+        the plan's dtype is the known sample under `fixed_mask` and the known bins' signal elsewhere, `fixed_mask` (batch, length)
+        bool / uint8 or None.  Both None clears the constraint; so does every `*_init`.  The plan keeps copies."""
+        self._sync_stream()
+        if offset is None:
+            assert fixed_mask is None, "a fixed_mask needs an offset"
+            _lib.check(self.lib.specinv_agla_constrain(self._h, None, None))
+            return
+        off = self._in(offset, self.dtype, (self.batch, self.length))
+        w = None
+        if fixed_mask is not None:
+            assert fixed_mask.dtype in (torch.bool, torch.uint8), f"fixed_mask must be bool or uint8, got {fixed_mask.dtype}"
+            w = self._in(fixed_mask.to(torch.uint8), torch.uint8, (self.batch, self.length))
+        _lib.check(self.lib.specinv_agla_constrain(self._h, off.data_ptr(), None if w is None else w.data_ptr()))
+
     def agla_iterate(self, n_iter: int, eval_last: bool = False):
         """`n_iter` AGLA iterations (projection launch + extrapolation launch each); the evaluation sums of the last if asked."""
         self._sync_stream()
