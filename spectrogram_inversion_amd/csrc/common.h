@@ -186,6 +186,22 @@ __device__ __forceinline__ double wave_scan_inclusive(double v) {
   return v;
 }
 
+// The phase of phase_init is a cumulative sum over time (methods.py:611) of up to 1e5 rad, and what follows it answers a change of
+// the start with a factor of hundreds: in float64 an ulp of that sum, the difference between two orders of summation, shows in
+// the gradients at 1e-9.  So float64 sums the way the reference's cumsum does on the CPU, one addition after the other from
+// `carry` in lane order (every lane runs the same 64 additions and keeps its own prefix); float32 rounds the double sum to
+// float32 and keeps the scan above.  Returns the lane's prefix, `carry` becomes lane 63's.
+__device__ __forceinline__ double wave_scan_in_order(double v, double& carry, int lane) {
+  double acc = carry, mine = 0;
+#pragma unroll 8
+  for (int l = 0; l < 64; ++l) {
+    acc += __shfl(v, l, 64);
+    if (l == lane) mine = acc;
+  }
+  carry = acc;
+  return mine;
+}
+
 constexpr int kWave = 64;
 constexpr int kMaxStages = 16;
 

@@ -165,9 +165,13 @@ __global__ void k_phase_init_adjoint_rows(const T* __restrict__ mag, const cplx<
       else if (peak_omega_adj<T>(col, Tn, f + 1, F, two_pi, T(n_fft), T(hop), w)) om = w;
     }
     double v = (double)om;
-    v = wave_scan_inclusive(v);
-    v += carry;
-    carry = __shfl(v, 63, 64);
+    if constexpr (std::is_same<T, double>::value) {
+      v = wave_scan_in_order(v, carry, lane);
+    } else {
+      v = wave_scan_inclusive(v);
+      v += carry;
+      carry = __shfl(v, 63, 64);
+    }
     if (t < Tn) {
       const T phi = (T)v;
       double s, c;

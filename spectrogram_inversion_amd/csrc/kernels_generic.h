@@ -1008,9 +1008,13 @@ __global__ void k_phase_init(const T* __restrict__ mag, cplx<T>* __restrict__ ou
     const T m0 = cur[2];
     if (t < Tn) om = scatter_omega<T>(cur, f, F, two_pi, T(n_fft), T(hop));
     double v = (double)om;
-    v = wave_scan_inclusive(v);
-    v += carry;
-    carry = __shfl(v, 63, 64);
+    if constexpr (std::is_same<T, double>::value) {
+      v = wave_scan_in_order(v, carry, lane);              // the reference's order of summation (common.h)
+    } else {
+      v = wave_scan_inclusive(v);
+      v += carry;
+      carry = __shfl(v, 63, 64);
+    }
     if (t < Tn) {
       const T phi = (T)v;                                  // :611
       double s, cs;

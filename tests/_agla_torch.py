@@ -23,8 +23,8 @@ from _util import hann
 from oracle.stftlib import signal_length
 
 
-def phase_init(mag, a):
-    """(B, F, T) real -> (B, F, T) complex"""
+def phase_advance(mag, a):
+    """(B, F, T) real -> (B, F, T): the phase every bin advances by in its frame, the omega of the peak that owns it (0: none)"""
     dt = mag.dtype
     mid, up, dn = mag[:, 1:-1], mag[:, 2:], mag[:, :-2]
     peak = (mid > up) & (mid > dn)
@@ -43,8 +43,12 @@ def phase_init(mag, a):
     pk_above = torch.cat([zb, pk[:, :-1]], 1)
     phase = torch.where(pk_below, below, torch.zeros_like(mag))
     phase = torch.where(pk_above, above, phase)
-    phase = torch.where(pk, om, phase)                                         # ... its own if it is one itself
-    phi = torch.cumsum(phase, dim=2)
+    return torch.where(pk, om, phase)                                          # ... its own if it is one itself
+
+
+def phase_init(mag, a):
+    """(B, F, T) real -> (B, F, T) complex"""
+    phi = torch.cumsum(phase_advance(mag, a), dim=2)
     return torch.complex(mag * torch.cos(phi), mag * torch.sin(phi))
 
 

@@ -653,10 +653,44 @@ def g16_headline_2048():
     save("g16b_c2_headline", **out)
 
 
+G17_CASES = [("512_128_la3", 512, 128, 3, True, 0.5), ("1024_256_la3_asym", 1024, 256, 3, True, 0.99),
+             ("1024_128_la_default", 1024, 128, -1, True, 0.99), ("2048_512_la3_alpha0", 2048, 512, 3, True, 0.0),
+             ("2048_512_la2_sym", 2048, 512, 2, False, 0.5)]
+
+
+def g17_autograd_rtisi_sizes():
+    """Gradients of the reference's RTISI_LA at the frame sizes its adjoint kernel launches differently for (256 threads below
+    n_fft 1024, 512 from 1024, 1024 from 2048): float64, the magnitudes of tests/_gla_torch.py::wellcond's STFT (computed in float32,
+    so float32-representable), batch 2, 16 frames, 2 inner iterations.  One file per case (each below 1 MiB): the magnitudes and the
+    weights of the loss sum(w y) as float32, y and the gradient as float64, and the reference's own sensitivity - the relative change
+    of its gradient when every magnitude is multiplied by 1 +- 2^-52 with random signs (rng 52), the yardstick of the test's gate."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _gla_torch as gt
+    for tag, n_fft, hop, la, asym, alpha in G17_CASES:
+        kw = dict(hop_length=hop, window=hann(n_fft, np.float32))
+        mag = np.abs(gt.wellcond_spec(2, n_fft, 16, kw, 170 + n_fft + hop)[0]).astype(np.float32)
+        kw64 = dict(hop_length=hop, window=t(hann(n_fft, np.float64)))
+
+        def run(m):
+            spec = t(m).requires_grad_(True)
+            y = M.RTISI_LA(spec, look_ahead=la, asymmetric_window=asym, max_iter=2, alpha=alpha, verbose=False, **kw64)
+            return spec, y
+
+        spec, y = run(mag.astype(np.float64))
+        wv = np.random.default_rng(17).standard_normal(tuple(y.shape)).astype(np.float32)
+        (y * t(wv.astype(np.float64))).sum().backward()
+        spec1, y1 = run(gt.ulp_perturbed(mag.astype(np.float64), np.random.default_rng(52)))
+        (y1 * t(wv.astype(np.float64))).sum().backward()
+        sens = float((spec1.grad - spec.grad).norm() / spec.grad.norm())
+        print(f"  g17 {tag}: sens64 {sens:.2e}")
+        save(f"g17_autograd_rtisi_sizes_{tag}", mag=mag, w=wv, y=y.detach().numpy(), grad=spec.grad.numpy(), sens64=np.array(sens),
+             meta=np.array(f"{n_fft}|{hop}|{la}|{int(asym)}|{alpha}|2"))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17"]
     table = dict(g0=g0_stft, g1=g1_phase_init, g2=g2_gla, g3=g3_sweep, g4=g4_admm, g5=g5_rtisi,
                  g6=g6_lbfgs, g7=g7_metrics, g8=g8_f64, g9=g9_lbfgs_rosen, g10=g10_autograd, g11=g11_autograd_admm, g12=g12_autograd_rtisi, g13=g13_wave_level_shapes,
-                 g14=g14_wellcond, g15=g15_wellcond_1024, g16=g16_headline_2048)
+                 g14=g14_wellcond, g15=g15_wellcond_1024, g16=g16_headline_2048, g17=g17_autograd_rtisi_sizes)
     for w in which:
         table[w]()

@@ -256,3 +256,105 @@ def test_backward_twice_with_retain_graph(fn, kw):
     assert torch.equal(g1, g2) and g1.abs().sum() > 0
     with pytest.raises(RuntimeError, match="second time|already been freed"):
         torch.autograd.grad(y.square().sum(), spec)
+
+
+# ---- real frame sizes, against the torch restatement of the recursions (tests/_gla_torch.py) -----------------------------------------
+# Three iterations, alpha 0.5 / rho 0.1, loss sum(w y), the magnitudes of a well-conditioned signal.  A float64 gradient from a
+# magnitude start is pinned end to end (phase_init_adjoint beyond 64 frames, the in-place transform); a float32 one only from a
+# complex start - through phase_init the reference's own float32 gradient is 5e-3 to 3e-1 from its float64 one at these shapes
+# (DESIGN 3.9).  tests/test_gla_torch_host.py admits every case by its conditioning, measured on the CPU alone.
+import _gla_torch as gt                                               # noqa: E402
+
+
+def _run_case(name, dtype):
+    method = gt.split(name)[0]
+    spec, w, kw = gt.inputs(name, dtype)
+    kw = dict(kw, window=torch.from_numpy(kw["window"]))
+    s = T(spec).requires_grad_(True)
+    if method == "gla":
+        y = si.griffin_lim(s, max_iter=gt.N_ITER, alpha=gt.COEF[method], tol=0, verbose=False, **kw)
+    else:
+        y = si.ADMM(s, max_iter=gt.N_ITER, rho=gt.COEF[method], tol=0, verbose=False, **kw)
+    assert y.requires_grad
+    (y * T(w)).sum().backward()
+    assert s.grad is not None and s.grad.shape == s.shape and s.grad.dtype == s.dtype
+    return N(y), N(s.grad)
+
+
+@pytest.mark.parametrize("name", gt.CASES_F64_MAG)
+def test_float64_gradient_from_magnitudes_at_frame_sizes(name):
+    """y to 1e-10, the gradient to max(1e-9, 100 x sens64).  The gradient answers a change of the start C0 = phase_init(mag) with a
+    factor of 100 to 700, and the phase in C0 is a cumulative sum of up to 1e5 rad: with that sum taken in wave-scan order the start was
+    an ulp of the sum (1e-11) from the reference's and the gradients at 2048/512 x 70 and 400/160 x 70 were 1.2e-9 to 4.1e-9 off.
+    Float64 now sums in the reference's order (common.h, wave_scan_in_order): y 2e-15 to 5e-14, gradients 1e-13 to 1.6e-11 (one MI355X)."""
+    y, grad = _run_case(name, np.float64)
+    y_ref, g_ref = gt.reference(name, np.float64)
+    sens = gt.sens64(name)
+    gate = max(1e-9, 100 * sens)               # 100 x: room for another, equally valid operation order over the one-ulp response
+    ey, eg = rel_l2(y, y_ref), rel_l2(grad, g_ref)
+    print(f"{name} float64: y {ey:.2e} grad {eg:.2e} (sens64 {sens:.2e}, gate {gate:.2e})")
+    assert ey <= 1e-10 and eg <= gate, (name, ey, eg, gate)
+
+
+@pytest.mark.parametrize("name", gt.CASES_F32_COMPLEX)
+def test_float32_gradient_from_a_complex_start_at_frame_sizes(name):
+    """Against the float64 restatement on the same float32 inputs; the yardstick is the restatement's own float32 error."""
+    y, grad = _run_case(name, np.float32)
+    y_ref, g_ref = gt.reference(name, np.float32, np.float64)
+    noise, y_noise = gt.noise32(name), rel_l2(gt.reference(name, np.float32)[0], y_ref)
+    gate, y_gate = max(2e-4, 6 * noise), max(1e-5, 6 * y_noise)
+    ey, eg = rel_l2(y, y_ref), rel_l2(grad, g_ref)
+    print(f"{name} float32: y {ey:.2e} (gate {y_gate:.2e}) grad {eg:.2e} (noise32 {noise:.2e}, gate {gate:.2e})")
+    assert ey <= y_gate and eg <= gate, (name, ey, y_gate, eg, gate)
+
+
+@pytest.mark.parametrize("name", gt.CASES_F64_COMPLEX)
+def test_float64_gradient_from_a_complex_start_at_frame_sizes(name):
+    y, grad = _run_case(name, np.float64)
+    y_ref, g_ref = gt.reference(name, np.float64)
+    ey, eg = rel_l2(y, y_ref), rel_l2(grad, g_ref)
+    print(f"{name} float64: y {ey:.2e} grad {eg:.2e}")
+    assert ey <= 1e-10 and eg <= 1e-9, (name, ey, eg)
+
+
+@pytest.mark.parametrize("shape", ["1024/256x80", "2048/512x70"])
+@pytest.mark.parametrize("method", ["gla", "admm"])
+@pytest.mark.parametrize("dtype,start,tol", [(np.float64, "mag", 1e-10), (np.float32, "complex", 2e-5)], ids=["f64 mag", "f32 complex"])
+def test_recorded_forward_equals_the_inference_path_at_frame_sizes(method, shape, dtype, start, tol):
+    """The waveform under grad (the recorded, staged forward) against the same call under no_grad (the fused kernels).  In float32
+    from the complex start: from magnitudes the forward is as ill-conditioned as its gradient."""
+    spec, _, kw = gt.inputs(f"{method} {shape} {start}", dtype)
+    kw = dict(kw, window=torch.from_numpy(kw["window"]))
+    fn = (lambda s: si.griffin_lim(s, max_iter=gt.N_ITER, alpha=0.5, tol=0, verbose=False, **kw)) if method == "gla" else \
+        (lambda s: si.ADMM(s, max_iter=gt.N_ITER, rho=0.1, tol=0, verbose=False, **kw))
+    y1 = fn(T(spec).requires_grad_(True))
+    with torch.no_grad():
+        y0 = fn(T(spec))
+    assert y1.requires_grad and not y0.requires_grad
+    err = rel_l2(N(y1), N(y0))
+    print(f"{method} {shape} {np.dtype(dtype).name} {start}: recorded forward against the inference path {err:.2e}")
+    assert err <= tol, err
+
+
+# ---- RTISI_LA at the frame sizes its adjoint kernel launches differently for -----------------------------------------------------------
+G17 = ["512_128_la3", "1024_256_la3_asym", "1024_128_la_default", "2048_512_la3_alpha0", "2048_512_la2_sym"]
+
+
+@pytest.mark.parametrize("tag", G17)
+def test_rtisi_gradient_at_launch_sizes(tag):
+    """k_rtisi_adjoint runs on 256 threads below n_fft 1024, 512 from 1024 and 1024 from 2048: the reference's float64 autograd on the
+    well-conditioned magnitudes, 16 frames, 2 inner iterations (g17_autograd_rtisi_sizes_*).  The gradient's gate is 100 x the
+    reference's own response to a one-ulp change of the magnitudes, stored with the fixture (at most 1e-8)."""
+    g = load_golden(f"g17_autograd_rtisi_sizes_{tag}")
+    n_fft, hop, la, asym, alpha, iters = str(g["meta"]).split("|")
+    n_fft, hop = int(n_fft), int(hop)
+    spec = T(g["mag"].astype(np.float64)).requires_grad_(True)
+    y = si.RTISI_LA(spec, look_ahead=int(la), asymmetric_window=bool(int(asym)), max_iter=int(iters), alpha=float(alpha), verbose=False,
+                    hop_length=hop, window=torch.from_numpy(hann(n_fft, np.float64)))
+    assert y.requires_grad
+    (y * T(g["w"].astype(np.float64))).sum().backward()
+    sens = float(g["sens64"])
+    gate = max(1e-9, 100 * sens)
+    ey, eg = rel_l2(N(y), g["y"]), rel_l2(N(spec.grad), g["grad"])
+    print(f"RTISI_LA {tag}: y {ey:.2e} grad {eg:.2e} (stored sens64 {sens:.2e}, gate {gate:.2e})")
+    assert ey <= 1e-9 and eg <= gate, (tag, ey, eg, gate)
