@@ -687,6 +687,11 @@ __global__ __launch_bounds__(MAXT) void k_iter_pair(FrameCfg<T> c, const T* __re
     lds_fft<T, IP>(a, b, c, false, -1, 0, twp);
     const int64_t base_a = ((int64_t)bi * c.n_frames + ta) * F, base_b = ((int64_t)bi * c.n_frames + tb) * F;
     const bool has_b = tb >= 0;
+    // A frame whose updated spectrum is all zeros (a silent frame of a zero-padded batch: target 0) has the inverse transform 0,
+    // exactly, in the reference; as the imaginary (real) part of the pair's complex transform it would pick up the rounding of its
+    // partner's frame - 1e-8 of a full-scale neighbour written into samples the reference returns as 0.0.  Such a frame is stored
+    // as zeros.
+    int nz_a = 0, nz_b = 0;
     if (c.onesided) {
       // spectra of the two frames at bin f (bin g = N - f holds their conjugates) -> updated Hermitian parts
       auto bin = [&](int f, T ma, cplx<T> a0, cplx<T> a1, T mb, cplx<T> b0, cplx<T> b1) {
@@ -707,6 +712,8 @@ __global__ __launch_bounds__(MAXT) void k_iter_pair(FrameCfg<T> c, const T* __re
           ha.y = T(0);
           hb.y = T(0);
         }
+        nz_a |= (ha.x != T(0)) | (ha.y != T(0));
+        nz_b |= (hb.x != T(0)) | (hb.y != T(0));
         b[f] = mk<T>(ha.x - hb.y, ha.y + hb.x);
         if (g != f) b[g] = mk<T>(ha.x + hb.y, hb.x - ha.y);
       };
@@ -731,11 +738,14 @@ __global__ __launch_bounds__(MAXT) void k_iter_pair(FrameCfg<T> c, const T* __re
         // Hermitian parts of the updated spectra at bin f
         const cplx<T> ha = mk<T>(T(0.5) * (yaf.x + yag.x), T(0.5) * (yaf.y - yag.y));
         const cplx<T> hb = mk<T>(T(0.5) * (ybf.x + ybg.x), T(0.5) * (ybf.y - ybg.y));
+        nz_a |= (ha.x != T(0)) | (ha.y != T(0));
+        nz_b |= (hb.x != T(0)) | (hb.y != T(0));
         b[f] = mk<T>(ha.x - hb.y, ha.y + hb.x);
         if (g != f) b[g] = mk<T>(ha.x + hb.y, hb.x - ha.y);
       }
     }
-    __syncthreads();
+    const bool live_a = __syncthreads_or(nz_a);            // (also the barrier after the update)
+    const bool live_b = __syncthreads_or(nz_b);
     {
       cplx<T>* tmp = a;
       a = b;
@@ -746,8 +756,8 @@ __global__ __launch_bounds__(MAXT) void k_iter_pair(FrameCfg<T> c, const T* __re
     T* fb = frames + ((int64_t)bi * c.n_frames + tb) * N;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
       const T w = c.window[n];
-      fa[n] = (a[n].x * c.inv_scale) * w;
-      if (has_b) fb[n] = (a[n].y * c.inv_scale) * w;
+      fa[n] = live_a ? (a[n].x * c.inv_scale) * w : T(0);
+      if (has_b) fb[n] = live_b ? (a[n].y * c.inv_scale) * w : T(0);
     }
     if (!split) break;
     ta = t0 + 1;          // second pass: the other frame on its own
@@ -821,6 +831,7 @@ __global__ void k_iter_pair_dr(FrameCfg<T> c, const T* __restrict__ x, cplx<T>* 
     const int64_t base_a = ((int64_t)bi * c.n_frames + ta) * F, base_b = ((int64_t)bi * c.n_frames + tb) * F;
     const bool has_b = tb >= 0;
     const cplx<T> zero = mk<T>(T(0), T(0));
+    int nz_a = 0, nz_b = 0;                                  // an all-zero updated spectrum is stored as a frame of zeros (k_iter_pair)
     // one thread owns the bin pair (f, N - f) of both frames: it reads and rewrites their two positions
     for (int f = threadIdx.x; f <= N / 2; f += blockDim.x) {
       const int g = f ? N - f : 0;
@@ -844,6 +855,8 @@ __global__ void k_iter_pair_dr(FrameCfg<T> c, const T* __restrict__ x, cplx<T>* 
           ha.y = T(0);
           hb.y = T(0);
         }
+        nz_a |= (ha.x != T(0)) | (ha.y != T(0));
+        nz_b |= (hb.x != T(0)) | (hb.y != T(0));
         a[pf] = mk<T>(ha.x - hb.y, ha.y + hb.x);
         if (g != f) a[pg] = mk<T>(ha.x + hb.y, hb.x - ha.y);
       } else {
@@ -857,19 +870,22 @@ __global__ void k_iter_pair_dr(FrameCfg<T> c, const T* __restrict__ x, cplx<T>* 
         // Hermitian parts of the updated spectra at bin f
         const cplx<T> ha = mk<T>(T(0.5) * (yaf.x + yag.x), T(0.5) * (yaf.y - yag.y));
         const cplx<T> hb = mk<T>(T(0.5) * (ybf.x + ybg.x), T(0.5) * (ybf.y - ybg.y));
+        nz_a |= (ha.x != T(0)) | (ha.y != T(0));
+        nz_b |= (hb.x != T(0)) | (hb.y != T(0));
         a[pf] = mk<T>(ha.x - hb.y, ha.y + hb.x);
         if (g != f) a[pg] = mk<T>(ha.x + hb.y, hb.x - ha.y);
       }
     }
-    __syncthreads();
+    const bool live_a = __syncthreads_or(nz_a);            // (also the barrier after the update)
+    const bool live_b = __syncthreads_or(nz_b);
     dr_fft_inv<T>(a, tab, lg8, c);
     T* fa = frames + ((int64_t)bi * c.n_frames + ta) * N;
     T* fb = frames + ((int64_t)bi * c.n_frames + tb) * N;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
       const T w = c.window[n];
       const cplx<T> v = a[dr_phys(n)];
-      fa[n] = (v.x * c.inv_scale) * w;
-      if (has_b) fb[n] = (v.y * c.inv_scale) * w;
+      fa[n] = live_a ? (v.x * c.inv_scale) * w : T(0);
+      if (has_b) fb[n] = live_b ? (v.y * c.inv_scale) * w : T(0);
     }
     if (!split) break;
     ta = t0 + 1;          // second pass: the other frame on its own
