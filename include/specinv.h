@@ -277,6 +277,27 @@ int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t
  * to the start. */
 int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
                                void* gmag_fm_accum);
+/* the backward sweep of constrained_unfolded (csrc/kernels_cgla_adjoint.h): the three entries above under the constraint of
+ * specinv_agla_constrain, in their argument order and with their error rules.  fixed_mask is W, (batch, length) uint8, non-zero where
+ * the sample is known, or NULL: no sample is.  goff_accum (batch, length) accumulates the cotangent of offset = where(W, xk, k).
+ * Iteration n >= 2 is t_n = where(W, offset, (1 - gamma_n) d_{n-1} + gamma_n (P(c_{n-1}) + offset)); with s as above and
+ * s' = W ? 0 : s, what passes the select:
+ *   dots_dev_out = {<gc, delta>, <gd, delta>, <s', t_n - d_{n-1}> / gamma_n};
+ *   goff_accum += W ? s : gamma_n s' ;
+ *   a <- -alpha_n gc - beta_n gd ;  gd <- (1 - gamma_n) s' ;  gc <- gamma_n s' / envelope ;  c_prev_out <- c_{n-1}.
+ * SPECINV_EINVAL before anything is enqueued: those of specinv_agla_extrap_adjoint, a NULL goff_accum. */
+int specinv_cgla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                                const void* fixed_mask, void* a_inout, void* gc_inout, void* gd_inout, void* goff_accum,
+                                void* c_prev_out, void* dots_dev_out);
+/* ... followed by the adjoint of the projection of iteration n at c_prev_out; mag_fm is where(M, 0, m) in frame-major layout, made
+ * once per sweep, M the mask of known bins. */
+int specinv_cgla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                              const void* fixed_mask, void* a_inout, void* gc_inout, void* gd_inout, void* goff_accum,
+                              void* c_prev_out, void* dots_dev_out, const void* mag_fm, void* gmag_fm_accum);
+/* the closing step, iteration 1: t_1 = c_1 = d_1 = where(W, offset, P(c_0) + offset).  With s = a + gc + gd (gd NULL: absent):
+ * goff_accum += s ; gc_inout <- (W ? 0 : s) / envelope, then the projection's adjoint at c0: gc_inout receives the cotangent of c0. */
+int specinv_cgla_first_adjoint(specinv_plan* plan, const void* c0, const void* fixed_mask, const void* a, void* gc_inout, const void* gd,
+                               void* goff_accum, const void* mag_fm, void* gmag_fm_accum);
 /* ---- one projection as a layer (gla_projection; csrc/kernels_proj_adjoint.h) ---------------
  * y = P(x; m) = ISTFT(m S / (|S| + 1e-16)), S = STFT(x): one Griffin-Lim iteration without momentum (methods.py:241-248), on
  * signals.  x and y_out are (batch, length), mag_fm is frame-major, (batch, n_frames, n_freq); y_out must not alias x.  All three

@@ -21,6 +21,6 @@ from .mel import mel_filterbank                                         # noqa: 
 from .mel_inverse import mel_to_stft, mel_to_audio, mel_to_stft_unfolded, mel_to_audio_unfolded   # noqa: E402,F401
 from .misi import misi, misi_unfolded                                   # noqa: E402,F401
 from .agla import accelerated_griffin_lim, agla_unfolded                # noqa: E402,F401
-from .constrained import constrained_griffin_lim                       # noqa: E402,F401
+from .constrained import constrained_griffin_lim, constrained_unfolded  # noqa: E402,F401
 from .projection import gla_projection, stft, istft                     # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

@@ -102,6 +102,9 @@ SIGNATURES = {
     "specinv_agla_extrap_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P]),
     "specinv_agla_step_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P, _P, _P]),
     "specinv_agla_first_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "specinv_cgla_extrap_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P, _P, _P]),
+    "specinv_cgla_step_adjoint": (C.c_int, [_P, _P, _P, _P, _DP, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "specinv_cgla_first_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "specinv_project": (C.c_int, [_P, _P, _P, _P]),
     "specinv_project_adjoint": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "specinv_project_adjoint_kind": (C.c_int, [_P, C.POINTER(C.c_int32)]),

@@ -129,4 +129,7 @@ __global__ void __launch_bounds__(256) k_agla_step_adjoint(AglaAdjArgs<T> p) {
 template <typename T>
 int agla_step_adjoint_launch(AglaAdjArgs<T> p, int batch, double* dots_dev, hipStream_t stream);
 
+// The finishing launch alone, for the sweeps that share it (kernels_cgla_adjoint.h): n_part partial triples -> dots_dev.
+int agla_dots_finish_launch(const double* partials, int n_part, double gamma, double* dots_dev, hipStream_t stream);
+
 }  // namespace specinv

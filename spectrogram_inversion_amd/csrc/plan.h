@@ -84,6 +84,15 @@ struct PlanBase {
   virtual int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
                                 void* gd, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) = 0;
   virtual int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) = 0;
+  // constrained AGLA's backward sweep (kernels_cgla_adjoint.h): the same three with the sample mask (nullptr: no known sample) and
+  // goff, the accumulated cotangent of the constraint's offset; stateless
+  virtual int cgla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask,
+                                  void* a, void* gc, void* gd, void* goff, void* c_prev, void* dots_dev) = 0;
+  virtual int cgla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask,
+                                void* a, void* gc, void* gd, void* goff, void* c_prev, void* dots_dev, const void* mag_fm,
+                                void* gmag_fm) = 0;
+  virtual int cgla_first_adjoint(const void* c0, const void* fixed_mask, const void* a, void* gc, const void* gd, void* goff,
+                                 const void* mag_fm, void* gmag_fm) = 0;
   // gla_projection: y = ISTFT(m S / (|S| + 1e-16)), S = STFT(x), and its adjoint - one fused launch where
   // project_adjoint_kind() is 1, else the stages of the sweeps above; stateless
   virtual int project(const void* x, const void* mag_fm, void* y_out) = 0;

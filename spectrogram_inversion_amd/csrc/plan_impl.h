@@ -21,6 +21,7 @@
 #include "kernels_misi_adjoint.h"
 #include "kernels_agla_adjoint.h"
 #include "kernels_cgla.h"
+#include "kernels_cgla_adjoint.h"
 #include "proj_adjoint_api.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
@@ -1230,6 +1231,64 @@ struct PlanT final : PlanBase {
     p.L = length;
     p.first = 1;
     SI_TRY(agla_step_adjoint_launch<T>(p, B(), nullptr, stream));
+    return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
+  }
+
+  // The adjoint of constrained AGLA's extrapolation step n >= 2 (kernels_cgla_adjoint.h): agla_extrap_adjoint with the sample mask
+  // (nullptr: no known sample) and goff, which it accumulates.  Only agla_adj_part is written beside the caller's arrays.
+  int cgla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask, void* a,
+                          void* gc, void* gd, void* goff, void* c_prev, void* dots_dev) override {
+    SI_CHECK(t_n && t_nm1 && coef && a && gc && goff && c_prev && dots_dev, SPECINV_EINVAL, "null pointer");
+    SI_CHECK(coef[0] >= 0 && coef[1] >= 0 && coef[3] >= 0 && coef[4] >= 0 && coef[2] > 0, SPECINV_EINVAL,
+             "alpha and beta must be >= 0, gamma > 0");
+    SI_CHECK(gd != nullptr || coef[2] == 1.0, SPECINV_EINVAL, "gamma = %g needs gd", coef[2]);
+    SI_TRY(agla_adj_part.reserve((size_t)3 * kAglaAdjMaxGrid * sizeof(double)));
+    CglaAdjArgs<T> p{};
+    p.a = static_cast<T*>(a);
+    p.gc = static_cast<T*>(gc);
+    p.gd = static_cast<T*>(gd);
+    p.goff = static_cast<T*>(goff);
+    p.tn = static_cast<const T*>(t_n);
+    p.tp = static_cast<const T*>(t_nm1);
+    p.tpp = static_cast<const T*>(t_nm2);
+    p.env = env.as<T>();
+    p.mask = static_cast<const uint8_t*>(fixed_mask);
+    p.c_prev = static_cast<T*>(c_prev);
+    p.partials = agla_adj_part.as<double>();
+    p.alpha = (T)coef[0];
+    p.beta = (T)coef[1];
+    p.gamma = (T)coef[2];
+    p.one_minus_gamma = (T)(1.0 - coef[2]);
+    p.alpha_p = (T)coef[3];
+    p.beta_p = (T)coef[4];
+    p.L = length;
+    return cgla_step_adjoint_launch<T>(p, B(), static_cast<double*>(dots_dev), stream);
+  }
+
+  // ... followed by the adjoint of the projection y = P(c_{n-1}) against mag_fm = where(M, 0, m): gc becomes the cotangent of c_{n-1}
+  int cgla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask, void* a,
+                        void* gc, void* gd, void* goff, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) override {
+    SI_CHECK(mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
+    SI_TRY(cgla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots_dev));
+    return proj_adjoint_stages(static_cast<T*>(gc), static_cast<const T*>(c_prev), static_cast<const T*>(mag_fm),
+                               static_cast<T*>(gmag_fm));
+  }
+
+  // The closing step t_1 = c_1 = d_1 = where(W, off, P(c_0) + off): s = a + gc + gd, goff += s, gc <- (W ? 0 : s) / env, then the
+  // projection's adjoint at c_0
+  int cgla_first_adjoint(const void* c0, const void* fixed_mask, const void* a, void* gc, const void* gd, void* goff, const void* mag_fm,
+                         void* gmag_fm) override {
+    SI_CHECK(c0 && a && gc && goff && mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
+    CglaAdjArgs<T> p{};
+    p.a = const_cast<T*>(static_cast<const T*>(a));
+    p.gc = static_cast<T*>(gc);
+    p.gd = const_cast<T*>(static_cast<const T*>(gd));
+    p.goff = static_cast<T*>(goff);
+    p.env = env.as<T>();
+    p.mask = static_cast<const uint8_t*>(fixed_mask);
+    p.L = length;
+    p.first = 1;
+    SI_TRY(cgla_step_adjoint_launch<T>(p, B(), nullptr, stream));
     return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
   }
 

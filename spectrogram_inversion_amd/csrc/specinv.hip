@@ -456,6 +456,34 @@ int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a
   ENTER(plan);
   return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum);
 }
+#define CGLA_ADJ_ARGS(name)                                                                     \
+  AGLA_ADJ_ARGS(name);                                                                          \
+  SI_CHECK(goff_accum, SPECINV_EINVAL, name ": NULL goff_accum")
+
+int specinv_cgla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                                const void* fixed_mask, void* a_inout, void* gc_inout, void* gd_inout, void* goff_accum,
+                                void* c_prev_out, void* dots_dev_out) {
+  CGLA_ADJ_ARGS("specinv_cgla_extrap_adjoint");
+  ENTER(plan);
+  return plan->impl->cgla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a_inout, gc_inout, gd_inout, goff_accum, c_prev_out,
+                                         dots_dev_out);
+}
+int specinv_cgla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
+                              const void* fixed_mask, void* a_inout, void* gc_inout, void* gd_inout, void* goff_accum,
+                              void* c_prev_out, void* dots_dev_out, const void* mag_fm, void* gmag_fm_accum) {
+  CGLA_ADJ_ARGS("specinv_cgla_step_adjoint");
+  SI_CHECK(mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_cgla_step_adjoint: NULL %s", mag_fm ? "gmag_fm_accum" : "mag_fm");
+  ENTER(plan);
+  return plan->impl->cgla_step_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a_inout, gc_inout, gd_inout, goff_accum, c_prev_out,
+                                       dots_dev_out, mag_fm, gmag_fm_accum);
+}
+int specinv_cgla_first_adjoint(specinv_plan* plan, const void* c0, const void* fixed_mask, const void* a, void* gc_inout, const void* gd,
+                               void* goff_accum, const void* mag_fm, void* gmag_fm_accum) {
+  SI_CHECK(c0 && a && gc_inout && goff_accum && mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_cgla_first_adjoint: NULL %s",
+           !c0 ? "c0" : !a ? "a" : !gc_inout ? "gc_inout" : !goff_accum ? "goff_accum" : !mag_fm ? "mag_fm" : "gmag_fm_accum");
+  ENTER(plan);
+  return plan->impl->cgla_first_adjoint(c0, fixed_mask, a, gc_inout, gd, goff_accum, mag_fm, gmag_fm_accum);
+}
 int specinv_project(specinv_plan* plan, const void* x, const void* mag_fm, void* y_out) {
   SI_CHECK(x && mag_fm && y_out, SPECINV_EINVAL, "specinv_project: NULL %s", !x ? "x" : !mag_fm ? "mag_fm" : "y_out");
   SI_CHECK(y_out != x, SPECINV_EINVAL, "specinv_project: y_out must not alias x");

@@ -43,12 +43,16 @@ int launch_v(const AglaAdjArgs<T>& p0, int batch, double* dots_dev, hipStream_t 
   else hipLaunchKernelGGL((k_agla_step_adjoint<T, V, false>), grid, blk, 0, stream, p);
   SI_HIP(hipGetLastError());
   if (p.first) return SPECINV_OK;
-  hipLaunchKernelGGL(k_agla_dots_finish, dim3(1), blk, 0, stream, p.partials, n_wg, (double)p.gamma, dots_dev);
-  SI_HIP(hipGetLastError());
-  return SPECINV_OK;
+  return agla_dots_finish_launch(p.partials, n_wg, (double)p.gamma, dots_dev, stream);
 }
 
 }  // namespace
+
+int agla_dots_finish_launch(const double* partials, int n_part, double gamma, double* dots_dev, hipStream_t stream) {
+  hipLaunchKernelGGL(k_agla_dots_finish, dim3(1), dim3(256), 0, stream, partials, n_part, gamma, dots_dev);
+  SI_HIP(hipGetLastError());
+  return SPECINV_OK;
+}
 
 template <typename T>
 int agla_step_adjoint_launch(AglaAdjArgs<T> p, int batch, double* dots_dev, hipStream_t stream) {

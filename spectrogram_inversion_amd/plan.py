@@ -506,6 +506,49 @@ class Plan:
                                                        None if gd is None else self._inout(gd, sig, "gd"), mag_fm.data_ptr(),
                                                        self._inout(gmag_fm, fm, "gmag_fm")))
 
+    def _fixed_mask(self, fixed_mask):
+        """The sample mask of the constrained sweep as (batch, length) uint8 on the device; None stays None."""
+        if fixed_mask is None:
+            return None
+        assert fixed_mask.dtype in (torch.bool, torch.uint8), f"fixed_mask must be bool or uint8, got {fixed_mask.dtype}"
+        return self._in(fixed_mask.to(torch.uint8), torch.uint8, (self.batch, self.length))
+
+    def cgla_extrap_adjoint(self, t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots):
+        """`agla_extrap_adjoint` under the constraint of `agla_constrain` (`specinv_cgla_extrap_adjoint`): `fixed_mask`
+        (batch, length) bool / uint8 or None is the mask of known samples, `goff` (batch, length) gains the cotangent of the
+        constraint's offset."""
+        self._sync_stream()
+        w = self._fixed_mask(fixed_mask)
+        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
+        goff = self._inout(goff, (self.batch, self.length), "goff")
+        _lib.check(self.lib.specinv_cgla_extrap_adjoint(self._h, *ptrs[:4], None if w is None else w.data_ptr(), *ptrs[4:7], goff,
+                                                        *ptrs[7:]))
+
+    def cgla_step_adjoint(self, t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots, mag_fm, gmag_fm):
+        """`cgla_extrap_adjoint`, then the adjoint of the projection at `c_prev` (`specinv_cgla_step_adjoint`); `mag_fm` is the
+        target with zeros under the mask of known bins, frame-major."""
+        self._sync_stream()
+        fm = (self.batch, self.n_frames, self.n_freq)
+        mag_fm = self._in(mag_fm, self.dtype, fm)
+        w = self._fixed_mask(fixed_mask)
+        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
+        goff = self._inout(goff, (self.batch, self.length), "goff")
+        _lib.check(self.lib.specinv_cgla_step_adjoint(self._h, *ptrs[:4], None if w is None else w.data_ptr(), *ptrs[4:7], goff,
+                                                      *ptrs[7:], mag_fm.data_ptr(), self._inout(gmag_fm, fm, "gmag_fm")))
+
+    def cgla_first_adjoint(self, c0, fixed_mask, a, gc, gd, goff, mag_fm, gmag_fm):
+        """The closing step of the constrained sweep (`specinv_cgla_first_adjoint`): `agla_first_adjoint` with the select of the
+        known samples; `goff` gains the cotangent of the constraint's offset."""
+        self._sync_stream()
+        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
+        c0, mag_fm = self._in(c0, self.dtype, sig), self._in(mag_fm, self.dtype, fm)
+        w = self._fixed_mask(fixed_mask)
+        _lib.check(self.lib.specinv_cgla_first_adjoint(self._h, c0.data_ptr(), None if w is None else w.data_ptr(),
+                                                       self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
+                                                       None if gd is None else self._inout(gd, sig, "gd"),
+                                                       self._inout(goff, sig, "goff"), mag_fm.data_ptr(),
+                                                       self._inout(gmag_fm, fm, "gmag_fm")))
+
     @property
     def project_adjoint_kind(self) -> str:
         """How `project_adjoint` runs on this plan (`specinv_project_adjoint_kind`): "staged" - two transforms, the element-wise
