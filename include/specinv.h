@@ -138,6 +138,16 @@ int specinv_istft(specinv_plan* plan, const void* spec, void* x_out);
 int specinv_envelope(specinv_plan* plan, void* env_out);
 /* phase_init, methods.py:572-615: mag (B, F, T) real -> (B, F, T) complex */
 int specinv_phase_init(specinv_plan* plan, const void* mag, void* spec_out);
+/* The phase vocoder (not in the reference; csrc/kernels_pvoc.h): spec_in (B, F, n_frames_in) complex resampled along time to
+ * spec_out (B, F, T_out) complex, T_out the plan's frame count - the plan is made for the OUTPUT, the one the inversion that
+ * follows uses.  T_out must be the smallest n >= 1 with (double)n * rate >= n_frames_in; rate > 1 shortens.  With t_j = j * rate,
+ * i = floor(t_j), a = t_j - i and frames at and beyond n_frames_in read as +0 + 0i:
+ *     |P[j]| = a |S[i+1]| + (1 - a) |S[i]| ;  arg P[0] = arg S[0] ;  arg P[j+1] = arg P[j] + wrap(arg S[i+1] - arg S[i] - adv) + adv,
+ * adv = 2 pi k_s hop / n_fft (k_s the signed bin), wrap(x) = x - 2 pi round(x / 2 pi).  Everything after the two angles is
+ * float64 for both dtypes, the running sum included; the result is rounded once.  Stateless: a running method is not disturbed.
+ * SPECINV_EINVAL, before the device is touched: a NULL pointer, spec_out == spec_in, n_frames_in < 1, a rate that is not finite and
+ * positive, a NULL plan, a plan whose frame count is not T_out. */
+int specinv_phase_vocoder(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, void* spec_out);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

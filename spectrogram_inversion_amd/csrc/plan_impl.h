@@ -22,6 +22,7 @@
 #include "kernels_agla_adjoint.h"
 #include "kernels_cgla.h"
 #include "kernels_cgla_adjoint.h"
+#include "kernels_pvoc.h"
 #include "proj_adjoint_api.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
@@ -595,6 +596,11 @@ struct PlanT final : PlanBase {
                        static_cast<C*>(spec_out), B(), n_freq, Tn(), N(), cfg.hop_length);
     SI_HIP(hipGetLastError());
     return SPECINV_OK;
+  }
+
+  int phase_vocoder(const void* spec_in, int n_frames_in, double rate, void* spec_out) override {
+    return pvoc_launch<T>(static_cast<const C*>(spec_in), static_cast<C*>(spec_out), B(), n_freq, n_frames_in, Tn(), rate, N(),
+                          cfg.hop_length, stream);
   }
 
   int reduce3(const T* a, const T* b, int64_t n, double out3[3]) {

@@ -246,6 +246,20 @@ int specinv_phase_init(specinv_plan* plan, const void* mag, void* spec_out) {
   ENTER(plan);
   return plan->impl->phase_init(mag, spec_out);
 }
+int specinv_phase_vocoder(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, void* spec_out) {
+  // (the argument errors before the device is touched)
+  SI_CHECK(spec_in && spec_out, SPECINV_EINVAL, "specinv_phase_vocoder: NULL %s", spec_in ? "spec_out" : "spec_in");
+  SI_CHECK(spec_in != spec_out, SPECINV_EINVAL, "specinv_phase_vocoder: spec_out must not alias spec_in");
+  SI_CHECK(n_frames_in >= 1, SPECINV_EINVAL, "n_frames_in must be >= 1, got %d", n_frames_in);
+  SI_CHECK(rate > 0 && std::isfinite(rate), SPECINV_EINVAL, "rate must be finite and > 0, got %g", rate);
+  PLAN_OR_FAIL(plan);
+  const int64_t want = pvoc_stretched_frames(n_frames_in, rate);
+  SI_CHECK(want == (int64_t)plan->impl->cfg.n_frames, SPECINV_EINVAL,
+           "the plan holds %d frames, %d frames at rate %g stretch to %lld (make the plan for the output frame count)",
+           plan->impl->cfg.n_frames, n_frames_in, rate, (long long)want);
+  ENTER(plan);
+  return plan->impl->phase_vocoder(spec_in, n_frames_in, rate, spec_out);
+}
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]) {
   ENTER(plan);
   SI_CHECK(sums_host, SPECINV_EINVAL, "sums_host is NULL");
