@@ -148,6 +148,17 @@ int specinv_phase_init(specinv_plan* plan, const void* mag, void* spec_out);
  * SPECINV_EINVAL, before the device is touched: a NULL pointer, spec_out == spec_in, n_frames_in < 1, a rate that is not finite and
  * positive, a NULL plan, a plan whose frame count is not T_out. */
 int specinv_phase_vocoder(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, void* spec_out);
+/* Sample-rate conversion (not in the reference; csrc/kernels_resample.h): x (batch, n_in) -> y (batch, n_out), real device arrays of
+ * `dtype` (SPECINV_F32 / SPECINV_F64) on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is
+ * kept between calls.  With o : n = orig_freq : new_freq reduced, base = min(o, n) * rolloff, W = lowpass_filter_width and x read
+ * as zero outside 0 ... n_in - 1 (torchaudio's sinc_interp_hann resampling, per output sample):
+ *     y[m] = (base / o) sum_{s : |tau| < W} sinc(tau) cos^2(pi tau / (2 W)) x[s] ;  tau = base (s n - m o) / (o n) ,
+ * sinc(t) = sin(pi t) / (pi t).  n_out must be ceil(n * n_in / o).  Weights and sum are float64 for both dtypes; the result is
+ * rounded once.  o == n copies x.  Any batch: it is not a launch dimension of its own.  SPECINV_EINVAL, before the device is
+ * touched: a NULL pointer, y == x, batch or n_in < 1, orig_freq or new_freq < 1, lowpass_filter_width < 1, a rolloff outside (0, 1],
+ * an n_out that is not ceil(n * n_in / o), n_out * o beyond 62 bits, an unknown dtype.  At the launch: ceil(W o / base) of 2^30 or more. */
+int specinv_resample(const void* x, void* y, int64_t batch, int64_t n_in, int64_t n_out, int64_t orig_freq, int64_t new_freq,
+                     int32_t lowpass_filter_width, double rolloff, int32_t dtype, int32_t device, void* hip_stream);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

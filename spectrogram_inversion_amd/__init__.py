@@ -23,5 +23,6 @@ from .misi import misi, misi_unfolded                                   # noqa: 
 from .agla import accelerated_griffin_lim, agla_unfolded                # noqa: E402,F401
 from .constrained import constrained_griffin_lim, constrained_unfolded  # noqa: E402,F401
 from .projection import gla_projection, stft, istft                     # noqa: E402,F401
-from .timescale import phase_vocoder, time_stretch, stretched_frames    # noqa: E402,F401
+from .timescale import phase_vocoder, time_stretch, stretched_frames, pitch_shift   # noqa: E402,F401
+from .resample import resample                                          # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

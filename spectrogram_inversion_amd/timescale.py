@@ -17,6 +17,11 @@ The vocoder's output is far from a consistent spectrogram (|STFT(ISTFT(P))| miss
     y = si.time_stretch(x, 0.8, n_fft=1024, hop_length=256, window=w)                  # 25 % longer
     P = si.phase_vocoder(si.stft(x, 1024, hop_length=256, window=w), 0.8, hop_length=256, window=w)
 
+`pitch_shift` is the other half of the pair (`librosa.effects.pitch_shift`, `torchaudio.functional.pitch_shift`): `time_stretch` by
+2^(-n_steps / bins_per_octave), then `resample` (resample.py) back to the original rate and length.
+
+    z = si.pitch_shift(x, 22050, 4, n_fft=1024, hop_length=256, window=w)              # four semitones up, as long as x
+
 Not part of the reference's surface.
 """
 from __future__ import annotations
@@ -31,7 +36,7 @@ from . import methods as _m
 from .plan import _RECOGNISED, args_helper, get_plan, require_gpu, trim_plan_cache
 from .projection import _COMPLEX, _check_items
 
-__all__ = ["phase_vocoder", "time_stretch", "stretched_frames"]
+__all__ = ["phase_vocoder", "time_stretch", "stretched_frames", "pitch_shift"]
 
 _METHODS = ("accelerated_griffin_lim", "griffin_lim", "ADMM")
 _MAX_FRAMES = 2147483000
@@ -132,3 +137,47 @@ def time_stretch(x, rate, n_fft=None, max_iter=32, method="accelerated_griffin_l
         return istft(P, **stft_kwargs)
     run = {"accelerated_griffin_lim": accelerated_griffin_lim, "griffin_lim": griffin_lim, "ADMM": ADMM}[method]
     return run(P, max_iter=max_iter, **kwargs)
+
+
+def shift_rate(sample_rate, n_steps, bins_per_octave=12):
+    """(rate, orig) of `pitch_shift`: the rate `time_stretch` runs at, 2^(-n_steps / bins_per_octave), and the sampling rate
+    int(sample_rate / rate) its result is read at, which `resample` then converts back to `sample_rate` (torchaudio's two lines)."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate < 1:
+        raise ValueError(f"sample_rate must be an int >= 1, got {sample_rate!r}")
+    if isinstance(n_steps, bool) or not isinstance(n_steps, numbers.Real) or not math.isfinite(n_steps):
+        raise ValueError(f"n_steps must be a finite number, got {n_steps!r}")
+    if isinstance(bins_per_octave, bool) or not isinstance(bins_per_octave, int) or bins_per_octave < 1:
+        raise ValueError(f"bins_per_octave must be an int >= 1, got {bins_per_octave!r}")
+    try:
+        rate = 2.0 ** (-float(n_steps) / bins_per_octave)
+        orig = int(sample_rate / rate)
+    except (OverflowError, ZeroDivisionError):
+        rate, orig = 0.0, 0
+    if not (rate > 0 and math.isfinite(rate) and orig >= 1):
+        raise ValueError(f"{n_steps} steps of {bins_per_octave} per octave at {sample_rate} Hz leave no sampling rate to convert from")
+    return rate, orig
+
+
+def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_iter=32, method="accelerated_griffin_lim",
+                lowpass_filter_width=6, rolloff=0.99, **kwargs):
+    r"""A waveform (L,) / (B, L) sampled at `sample_rate` raised by `n_steps` steps of `bins_per_octave` to the octave (a real
+    number: fractional and negative steps are valid) at the same duration: a waveform of the same shape.
+
+    It is exactly, with (rate, orig) = shift_rate(sample_rate, n_steps, bins_per_octave),
+
+        y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, **kwargs)
+        if orig != sample_rate:
+            y = resample(y, orig, sample_rate, lowpass_filter_width, rolloff)
+
+    and then y[..., :L], zero-padded on the right to L where it is shorter - torchaudio's definition, its phase vocoder refined by
+    `method`.  `**kwargs` are `time_stretch`'s; dtype and device rules are `time_stretch`'s and `resample`'s.
+    """
+    from .resample import resample
+    rate, orig = shift_rate(sample_rate, n_steps, bins_per_octave)
+    y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, **kwargs)
+    if orig != sample_rate:
+        y = resample(y, orig, sample_rate, lowpass_filter_width, rolloff)
+    n = x.shape[-1]
+    if y.shape[-1] >= n:
+        return y[..., :n]
+    return torch.nn.functional.pad(y, (0, n - y.shape[-1]))
