@@ -148,6 +148,17 @@ int specinv_phase_init(specinv_plan* plan, const void* mag, void* spec_out);
  * SPECINV_EINVAL, before the device is touched: a NULL pointer, spec_out == spec_in, n_frames_in < 1, a rate that is not finite and
  * positive, a NULL plan, a plan whose frame count is not T_out. */
 int specinv_phase_vocoder(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, void* spec_out);
+/* The same with a phase-locking mode (csrc/kernels_pvoc_lock.h).  SPECINV_PVOC_LOCK_NONE is specinv_phase_vocoder, bit for bit.
+ * SPECINV_PVOC_LOCK_IDENTITY is identity phase locking (Laroche & Dolson 1999): with S0 = S[i] and q[k] = re^2 + im^2 of S0[k] in
+ * float64, bin k is a peak of output frame j when q[k] > q[k'] for k' = k +- 1, k +- 2 (modulo n_fft on a two-sided spectrum, dropped
+ * outside 0 .. F - 1 on a one-sided one, dropped where k' + k = 0 mod n_fft: the bin's own mirror image); every bin takes the
+ * nearest peak p of its frame (circular distance on a two-sided spectrum; a tie goes to the smaller |k_s|, then to the lower
+ * index) and arg P[j][k] = (phi[p] - arg S0[p]) + arg S0[k], phi the unlocked running phase above, in float64; a frame without a
+ * peak keeps phi.  |P| is unchanged.  Two launches; the first identity call reserves batch * F * T_out doubles in the plan.
+ * The errors are specinv_phase_vocoder's, in its order; an unknown mode is SPECINV_EINVAL ("mode"), after the rate. */
+enum { SPECINV_PVOC_LOCK_NONE = 0, SPECINV_PVOC_LOCK_IDENTITY = 1 };
+int specinv_phase_vocoder_locked(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, int32_t mode,
+                                 void* spec_out);
 /* Sample-rate conversion (not in the reference; csrc/kernels_resample.h): x (batch, n_in) -> y (batch, n_out), real device arrays of
  * `dtype` (SPECINV_F32 / SPECINV_F64) on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is
  * kept between calls.  With o : n = orig_freq : new_freq reduced, base = min(o, n) * rolloff, W = lowpass_filter_width and x read

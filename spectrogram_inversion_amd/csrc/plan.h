@@ -43,6 +43,8 @@ struct PlanBase {
   virtual int metric_sums(const void* a, const void* b, int64_t n, double sums[4]) = 0;
   // the phase vocoder (kernels_pvoc.h): (B, F, n_frames_in) complex resampled along time to the plan's frames; stateless
   virtual int phase_vocoder(const void* spec_in, int n_frames_in, double rate, void* spec_out) = 0;
+  // ... with identity phase locking (kernels_pvoc_lock.h); reserves the plan's float64 phase scratch on its first call
+  virtual int phase_vocoder_locked(const void* spec_in, int n_frames_in, double rate, void* spec_out) = 0;
 
   virtual int gla_init(const void* init_spec, const void* mag, double alpha) = 0;
   virtual int admm_init(const void* init_spec, const void* mag, double rho) = 0;

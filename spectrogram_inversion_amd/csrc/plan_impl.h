@@ -23,6 +23,7 @@
 #include "kernels_cgla.h"
 #include "kernels_cgla_adjoint.h"
 #include "kernels_pvoc.h"
+#include "kernels_pvoc_lock.h"
 #include "proj_adjoint_api.h"
 #include "lbfgs_dev.h"
 #include "kernels_rtisi.h"
@@ -113,6 +114,7 @@ struct PlanT final : PlanBase {
   bool agla_general = false;            // ... some gamma != 1: d exists
   DevBuf agla_adj_part;                 // agla_*_adjoint: the workgroups' partial inner products
   int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
+  DevBuf pvoc_phi;                      // phase_vocoder_locked: the running phase as float64, (batch, n_freq, frames)
   DevBuf cgla_off, cgla_mask;           // agla_constrain: where(W, xk, k) and W, (batch, length) each (kernels_cgla.h); no p: none set
   bool proj_adj_fused = false;          // project_adjoint: k_wave_proj_adjoint (kernels_proj_adjoint.h) instead of the stages
   int proj_adj_max_waves = 0;           // ... SPECINV_PROJ_ADJ_WAVES: at most so many waves per launch (0: the chip's fill)
@@ -601,6 +603,12 @@ struct PlanT final : PlanBase {
   int phase_vocoder(const void* spec_in, int n_frames_in, double rate, void* spec_out) override {
     return pvoc_launch<T>(static_cast<const C*>(spec_in), static_cast<C*>(spec_out), B(), n_freq, n_frames_in, Tn(), rate, N(),
                           cfg.hop_length, stream);
+  }
+
+  int phase_vocoder_locked(const void* spec_in, int n_frames_in, double rate, void* spec_out) override {
+    SI_TRY(pvoc_phi.reserve((size_t)nspec() * sizeof(double)));
+    return pvoc_lock_launch<T>(static_cast<const C*>(spec_in), static_cast<C*>(spec_out), pvoc_phi.as<double>(), B(), n_freq,
+                               n_frames_in, Tn(), rate, N(), cfg.hop_length, !cfg.onesided, stream);
   }
 
   int reduce3(const T* a, const T* b, int64_t n, double out3[3]) {

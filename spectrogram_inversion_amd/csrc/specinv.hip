@@ -261,6 +261,24 @@ int specinv_phase_vocoder(specinv_plan* plan, const void* spec_in, int32_t n_fra
   ENTER(plan);
   return plan->impl->phase_vocoder(spec_in, n_frames_in, rate, spec_out);
 }
+int specinv_phase_vocoder_locked(specinv_plan* plan, const void* spec_in, int32_t n_frames_in, double rate, int32_t mode,
+                                 void* spec_out) {
+  // (specinv_phase_vocoder's argument errors in its order, then the mode)
+  SI_CHECK(spec_in && spec_out, SPECINV_EINVAL, "specinv_phase_vocoder_locked: NULL %s", spec_in ? "spec_out" : "spec_in");
+  SI_CHECK(spec_in != spec_out, SPECINV_EINVAL, "specinv_phase_vocoder_locked: spec_out must not alias spec_in");
+  SI_CHECK(n_frames_in >= 1, SPECINV_EINVAL, "n_frames_in must be >= 1, got %d", n_frames_in);
+  SI_CHECK(rate > 0 && std::isfinite(rate), SPECINV_EINVAL, "rate must be finite and > 0, got %g", rate);
+  SI_CHECK(mode == SPECINV_PVOC_LOCK_NONE || mode == SPECINV_PVOC_LOCK_IDENTITY, SPECINV_EINVAL,
+           "mode must be SPECINV_PVOC_LOCK_NONE or SPECINV_PVOC_LOCK_IDENTITY, got %d", mode);
+  if (mode == SPECINV_PVOC_LOCK_NONE) return specinv_phase_vocoder(plan, spec_in, n_frames_in, rate, spec_out);
+  PLAN_OR_FAIL(plan);
+  const int64_t want = pvoc_stretched_frames(n_frames_in, rate);
+  SI_CHECK(want == (int64_t)plan->impl->cfg.n_frames, SPECINV_EINVAL,
+           "the plan holds %d frames, %d frames at rate %g stretch to %lld (make the plan for the output frame count)",
+           plan->impl->cfg.n_frames, n_frames_in, rate, (long long)want);
+  ENTER(plan);
+  return plan->impl->phase_vocoder_locked(spec_in, n_frames_in, rate, spec_out);
+}
 int specinv_resample(const void* x, void* y, int64_t batch, int64_t n_in, int64_t n_out, int64_t orig_freq, int64_t new_freq,
                      int32_t lowpass_filter_width, double rolloff, int32_t dtype, int32_t device, void* hip_stream) {
   // (the argument errors before the device is touched)

@@ -226,14 +226,21 @@ class Plan:
         _lib.check(self.lib.specinv_phase_init(self._h, mag.data_ptr(), out.data_ptr()))
         return out
 
-    def phase_vocoder(self, spec: torch.Tensor, rate: float) -> torch.Tensor:
+    def phase_vocoder(self, spec: torch.Tensor, rate: float, phase_lock=None) -> torch.Tensor:
         """`spec` (batch, n_freq, T) complex resampled along time at `rate` to the plan's frames (`specinv_phase_vocoder`): the
-        plan is made for the output, `timescale.stretched_frames(T, rate)` frames."""
+        plan is made for the output, `timescale.stretched_frames(T, rate)` frames.  `phase_lock="identity"` locks the phase
+        around the spectral peaks (`specinv_phase_vocoder_locked`; its first call reserves batch * n_freq * frames doubles)."""
+        if phase_lock is not None and not (isinstance(phase_lock, str) and phase_lock in _lib.PVOC_LOCK):
+            raise ValueError(f"phase_lock must be None or 'identity', got {phase_lock!r}")
         self._sync_stream()
         assert spec.dim() == 3, f"expected (batch, n_freq, frames), got shape {tuple(spec.shape)}"
         spec = self._in(spec, self.cdtype, (self.batch, self.n_freq, spec.shape[2]))
         out = torch.empty(self._spec_shape(), dtype=self.cdtype, device=self.device)
-        _lib.check(self.lib.specinv_phase_vocoder(self._h, spec.data_ptr(), int(spec.shape[2]), float(rate), out.data_ptr()))
+        if phase_lock is None:
+            _lib.check(self.lib.specinv_phase_vocoder(self._h, spec.data_ptr(), int(spec.shape[2]), float(rate), out.data_ptr()))
+        else:
+            _lib.check(self.lib.specinv_phase_vocoder_locked(self._h, spec.data_ptr(), int(spec.shape[2]), float(rate),
+                                                             _lib.PVOC_LOCK[phase_lock], out.data_ptr()))
         return out
 
     def metric_sums(self, a: torch.Tensor, b: torch.Tensor):
