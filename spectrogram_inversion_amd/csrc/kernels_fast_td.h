@@ -38,6 +38,125 @@ __device__ __forceinline__ void td_load_block(const float* __restrict__ xrow, co
   else load_block<R, OV>(xrow, tailrow, L, T, c, t_begin, t_end, j, lane, pad_mode, q);
 }
 
+// ---- the n_fft 2048 transform as this file's kernels run it ----------------------------------------------------------------------
+// The same butterflies on the same values as fft_forward_t / fft_inverse_t<16> (fast_core.h), bit for bit, written for a frame loop
+// that is bound by the vector instructions it issues:
+//   * the one +-i rotation of the radix-16 (W_16^4 on a[10]) rides on the source modifiers of the two packed adds that read it
+//     instead of a v_xor + v_mov in front of them;
+//   * the transpose scratch is addressed from two per-lane LDS pointers.  The strided side (the rows a 16-lane row owns, up to
+//     8 KiB apart) goes through volatile accesses: one ds_read_b64 / ds_write_b64 each with the distance in the 16-bit offset
+//     field - left to the compiler's pairing into ds_read2 / ds_write2, whose offsets hold 8 bits, every pair gets a v_add_u32 of
+//     its own to re-base it.  The contiguous side pairs up within 8 bits of a pointer the compiler cannot fold the table's base
+//     into (td_scratch).  16 vector instructions per transform pair for 16 more LDS instructions; same rows, same pads.  The
+//     forward transform's single writes are free of bank conflicts like the pairs were; the inverse's 16 single reads are 2-way
+//     conflicted (the two 16-lane rows of a 32-lane read group lie 34 elements apart; a ds_read2_b64 serves 16 lanes at a time
+//     and never met that): SQ_LDS_BANK_CONFLICT 0 -> 32 cycles per frame, measured WITH the gain this form brings
+//     (profiles/frame_loop_trim.json).  Written through `tr` these reads pair up again - but `tr` is __restrict__ and the
+//     writes just before go through sc.b: every access of the n_fft 2048 path must stay on the two TdScratch pointers.
+// The other sizes, and the kernels of the other translation units, keep the shared text.
+using lds_v2f = __attribute__((address_space(3))) v2f;
+struct TdScratch {
+  volatile lds_v2f* q;     // tr + k.tr_q: the strided side
+  lds_v2f* b;              // tr + k.tr_b: the contiguous side
+};
+template <int R>
+__device__ __forceinline__ TdScratch td_scratch(v2f* tr, const LaneConst<R>& k) {
+  TdScratch s;
+  s.q = (volatile lds_v2f*)(tr + k.tr_q);
+  s.b = (lds_v2f*)(tr + k.tr_b);
+  asm volatile("" : "+v"(s.b));     // (opaque: the contiguous side's 16 offsets count from this register)
+  return s;
+}
+
+// dft4 of (a0, a1, rot<INV>(a2), a3)
+template <bool INV>
+__device__ __forceinline__ void dft4_rot2(v2f& a0, v2f& a1, v2f& a2, v2f& a3) {
+  const v2f t0 = INV ? add_i(a0, a2) : sub_i(a0, a2);
+  const v2f t1 = INV ? sub_i(a0, a2) : add_i(a0, a2);
+  const v2f t2 = a1 + a3, d = a1 - a3;
+  a0 = t0 + t2;
+  a2 = t0 - t2;
+  a1 = INV ? add_i(t1, d) : sub_i(t1, d);
+  a3 = INV ? sub_i(t1, d) : add_i(t1, d);
+}
+// Dft<16, INV, true>::run
+template <bool INV>
+__device__ __forceinline__ void td_dft16(v2f (&a)[16]) {
+  constexpr float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
+#pragma unroll
+  for (int n0 = 0; n0 < 4; ++n0) dft4<INV>(a[n0], a[n0 + 4], a[n0 + 8], a[n0 + 12]);
+  dirmul_x4<INV, true>(a[5], a[6], a[7], a[9], v2f{c1, -s1}, v2f{h, -h}, v2f{s1, -c1}, v2f{h, -h});
+  dirmul_x4<INV, true>(a[11], a[13], a[14], a[15], v2f{-h, -h}, v2f{s1, -c1}, v2f{-h, -h}, v2f{-c1, s1});
+  dft4<INV>(a[0], a[1], a[2], a[3]);
+  dft4<INV>(a[4], a[5], a[6], a[7]);
+  dft4_rot2<INV>(a[8], a[9], a[10], a[11]);
+  dft4<INV>(a[12], a[13], a[14], a[15]);
+  v2f o[16];
+#pragma unroll
+  for (int k0 = 0; k0 < 4; ++k0)
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) o[k1 + 4 * k0] = a[k0 + 4 * k1];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) a[i] = o[i];
+}
+
+template <int R, typename TW>
+__device__ __forceinline__ void td_fft_forward(v2f (&z)[R], const LaneConst<R>& k, const TW& tw, v2f* __restrict__ tr,
+                                               const TdScratch& sc) {
+  if constexpr (R == 16) {
+    td_dft16<false>(z);
+    cmul_all<R, true, false, 1>(z, tw);
+#pragma unroll
+    for (int g = 0; g < R; g += 4) xlane_dft4_in<false>(z[g], z[g + 1], z[g + 2], z[g + 3]);
+#pragma unroll
+    for (int g = 0; g < R; g += 4) {
+      z[g + 2] = cmul(z[g + 2], k.postq[0]);
+      z[g + 1] = cmul(z[g + 1], k.postq[1]);
+      z[g + 3] = cmul(z[g + 3], k.postq[2]);
+    }
+#pragma unroll
+    for (int g = 0; g < R; g += 4) {
+      sc.q[(0 * R + g) * (R + 1)] = z[g];
+      sc.q[(1 * R + g) * (R + 1)] = z[g + 2];
+      sc.q[(2 * R + g) * (R + 1)] = z[g + 1];
+      sc.q[(3 * R + g) * (R + 1)] = z[g + 3];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) z[i] = sc.b[i];
+    td_dft16<false>(z);
+  } else {
+    fft_forward_t<R>(z, k, tw, tr);
+  }
+}
+template <int R, typename TW>
+__device__ __forceinline__ void td_fft_inverse(v2f (&z)[R], const LaneConst<R>& k, const TW& tw, v2f* __restrict__ tr,
+                                               const TdScratch& sc) {
+  if constexpr (R == 16) {
+    td_dft16<true>(z);
+#pragma unroll
+    for (int i = 0; i < R; ++i) sc.b[i] = z[i];
+#pragma unroll
+    for (int g = 0; g < R; g += 4) {
+      z[g] = sc.q[(0 * R + g) * (R + 1)];
+      z[g + 2] = sc.q[(1 * R + g) * (R + 1)];
+      z[g + 1] = sc.q[(2 * R + g) * (R + 1)];
+      z[g + 3] = sc.q[(3 * R + g) * (R + 1)];
+    }
+#pragma unroll
+    for (int g = 0; g < R; g += 4) {
+      z[g + 2] = cmulc(z[g + 2], k.postq[0]);
+      z[g + 1] = cmulc(z[g + 1], k.postq[1]);
+      z[g + 3] = cmulc(z[g + 3], k.postq[2]);
+    }
+#pragma unroll
+    for (int g = 0; g < R; g += 4) xlane_dft4_out<true>(z[g], z[g + 1], z[g + 2], z[g + 3]);
+    cmul_all<R, true, true, 1>(z, tw);
+    td_dft16<true>(z);
+  } else {
+    fft_inverse_t<R>(z, k, tw, tr);
+  }
+}
+
 template <int R, int OV, bool EARLY, bool EVAL>
 __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   using G = Geo<R>;
@@ -67,6 +186,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);   // (scalar: the frame loop and its padding tests branch on the scalar unit; left to the compiler the work-group size may arrive in a vector register and make all of it per-lane)
   if (a.skew == 0 && w >= a.n_waves) return;     // (skewed chunks: the test follows the mapping, which permutes inside a workgroup)
   const LaneConst<R> k = lane_consts<R>();
+  const TdScratch tsc = td_scratch<R>(tr, k);
   const int lane = k.lane;
   const unsigned ulane = (unsigned)lane;
   // Even chunks: wave w walks chunk w mod nchunks of item w / nchunks.  Skewed chunks (a launch of exactly two waves per SIMD):
@@ -136,8 +256,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   // the same summands in the same order, plan_impl.h): one block of its reciprocal is kept in registers instead of being loaded for
   // every frame (the evaluating variant has no registers to spare and keeps loading)
   constexpr bool ENVREG = !EVAL;
-  v2f envc[ENVREG ? QU : 1];
-  v2f envr[ENVREG ? QU : 1];     // (the envelope block and its correctly rounded reciprocal)
+  v2f envc[QU], envr[QU];        // (the envelope block and its correctly rounded reciprocal)
   if (ENVREG) {
     const v2f* e0 = reinterpret_cast<const v2f*>(a.env + (long long)(NB - PB) * HOP);
 #pragma unroll
@@ -157,7 +276,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   for (int t = t_begin; t < t_end; ++t) {
     asm volatile("" ::: "memory");     // (window / twiddle reads stay inside the loop: hoisted they pin ~80 VGPRs)
     v2f wn = k.wn;
-    asm volatile("" : "+v"(wn));
+    if (!WKREG) asm volatile("" : "+v"(wn));     // (only the launches that rebuild the pair twiddles read it)
     const long long fi = (long long)b * a.T + t;
     v4f mm[H / 2];
     v4f pp[EARLY ? H : 1];
@@ -192,7 +311,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
 #pragma unroll
         for (int i = 0; i < QU; ++i) z[qq * QU + i] = q[i] * lds_win[64 * (qq * QU + i) + lane];
       }
-      fft_forward_t<R>(z, k, twr, tr);
+      td_fft_forward<R>(z, k, twr, tr, tsc);
       v2f rc[H];
 #pragma unroll
       for (int m = H; m < R; ++m) {
@@ -241,11 +360,17 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       for (int q = 0; q + 1 < NB; ++q) xq[q][i] = xq[q + 1][i];
       xq[NB - 1][i] = xn[i];
     }
-    if (t + 1 < t_end)
+    // (the block after a chunk's last frame has no reader: the empty asm defines xn there, so that the compiler does not carry
+    // the old block round the loader's arms in a second set of registers)
+    if (t + 1 < t_end) {
       td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
+    } else {
+#pragma unroll
+      for (int i = 0; i < QU; ++i) asm volatile("" : "=v"(xn[i]));
+    }
     __builtin_amdgcn_s_setprio(0);
 
-    fft_forward_t<R>(z, k, twr, tr);
+    td_fft_forward<R>(z, k, twr, tr, tsc);
 
     v2f rc[H];
 #pragma unroll
@@ -321,45 +446,41 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
     }
 
-    fft_inverse_t<R>(z, k, twr, tr);
+    td_fft_inverse<R>(z, k, twr, tr, tsc);
 
     // ---- synthesis window, register overlap-add, one finished hop-block of x_{t+1} and of z_{t+1} out
+    // (the newest quarter is multiplied where it is stored, after the shift below has read its slot: the product lands in the
+    // accumulator's registers instead of being moved there)
 #pragma unroll
-    for (int u = 0; u < R; ++u) z[u] = z[u] * lds_wins[64 * u + lane];
+    for (int u = 0; u < NB * QU; ++u) z[u] = z[u] * lds_wins[64 * u + lane];
     if (t >= PB) {
       const long long o0 = (long long)(t - PB) * HOP;
       const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);   // uniform
       v2f* xo = reinterpret_cast<v2f*>(xorow + o0);
       v2f* zo = reinterpret_cast<v2f*>(zorow + o0);
-      // The envelope block: the register copy wherever it is valid.  The first frames of an item load theirs - in an arm of
-      // its own that also waits for it (the empty asm reads the registers): left to a select per value the compiler puts each
-      // load behind a branch and an unconditional s_waitcnt vmcnt(0) after the join, which on gfx950 also waits for the stores
-      // just issued - three store round trips per frame in the steady state.
-      v2f ev[QU], er[QU];
+      // The envelope block: the register copy wherever it is valid, read where it lies.  The first frames of an item load theirs
+      // into it - in an arm of its own that also waits for it (the empty asm reads the registers): left to a select per value
+      // the compiler puts each load behind a branch and an unconditional s_waitcnt vmcnt(0) after the join, which on gfx950 also
+      // waits for the stores just issued - three store round trips per frame in the steady state.  Frame NB's block IS the
+      // periodic one (envp = a.env + (NB - PB) HOP there): the arm's last pass leaves it in the registers for the rest of the chunk.
       if (!ENVREG) {
 #pragma unroll
         for (int i = 0; i < QU; ++i) {
-          ev[i] = envp[64u * i + ulane];
-          er[i] = env_rcp(ev[i]);
+          envc[i] = envp[64u * i + ulane];
+          envr[i] = env_rcp(envc[i]);
         }
-      } else if (t >= NB) {
+      } else if (t <= NB) {
 #pragma unroll
-        for (int i = 0; i < QU; ++i) {
-          ev[i] = envc[ENVREG ? i : 0];
-          er[i] = envr[ENVREG ? i : 0];
-        }
-      } else {
+        for (int i = 0; i < QU; ++i) envc[i] = envp[64u * i + ulane];
 #pragma unroll
-        for (int i = 0; i < QU; ++i) ev[i] = envp[64u * i + ulane];
+        for (int i = 0; i < QU; ++i) asm volatile("" : "+v"(envc[i]));
 #pragma unroll
-        for (int i = 0; i < QU; ++i) asm volatile("" : "+v"(ev[i]));
-#pragma unroll
-        for (int i = 0; i < QU; ++i) er[i] = env_rcp(ev[i]);
+        for (int i = 0; i < QU; ++i) envr[i] = env_rcp(envc[i]);
       }
 #pragma unroll
       for (int i = 0; i < QU; ++i) {
-        const v2f xv = env_apply_r(acc[i] + z[i], ev[i], er[i]);
-        const v2f zv = v2f{fmaf(nlr, zold[i].x, xv.x), fmaf(nlr, zold[i].y, xv.y)};
+        const v2f xv = env_apply_r(acc[i] + z[i], envc[i], envr[i]);
+        const v2f zv = __builtin_elementwise_fma(v2f{nlr, nlr}, zold[i], xv);     // (one packed operation)
         if (write_x) xo[64u * i + ulane] = xv;
         zo[64u * i + ulane] = zv;
       }
@@ -368,8 +489,9 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     for (int i = 0; i < QU; ++i) {
 #pragma unroll
       for (int q = 0; q + 1 < NB; ++q) acc[q * QU + i] = acc[(q + 1) * QU + i] + z[(q + 1) * QU + i];
-      acc[(NB - 1) * QU + i] = z[NB * QU + i];
     }
+#pragma unroll
+    for (int i = 0; i < QU; ++i) acc[(NB - 1) * QU + i] = z[NB * QU + i] * lds_wins[64 * (NB * QU + i) + lane];
   }
   if (t_end == a.T) {
     // the chunk that holds the last frame also finishes hop-blocks T .. T + PB - 2 (the frames that reach them are done);
@@ -444,6 +566,7 @@ __global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wib);
   if (w >= a.n_waves * kEvalSub) return;
   const LaneConst<R> k = lane_consts<R>();
+  const TdScratch tsc = td_scratch<R>(tr, k);
   const int lane = k.lane;
   const unsigned ulane = (unsigned)lane;
   const int cw = w / kEvalSub, sub = w - cw * kEvalSub;
@@ -485,8 +608,13 @@ __global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a) {
       for (int q = 0; q + 1 < NB; ++q) xq[q][i] = xq[q + 1][i];
       xq[NB - 1][i] = xn[i];
     }
-    if (t + 1 < s_end) td_load_block<R, OV>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
-    fft_forward_t<R>(z, k, twr, tr);
+    if (t + 1 < s_end) {
+      td_load_block<R, OV>(xrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
+    } else {      // (no reader: see fused_td_body)
+#pragma unroll
+      for (int i = 0; i < QU; ++i) asm volatile("" : "=v"(xn[i]));
+    }
+    td_fft_forward<R>(z, k, twr, tr, tsc);
     v2f rc[H];
 #pragma unroll
     for (int m = H; m < R; ++m) {
