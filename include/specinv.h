@@ -170,6 +170,25 @@ int specinv_phase_vocoder_locked(specinv_plan* plan, const void* spec_in, int32_
  * an n_out that is not ceil(n * n_in / o), n_out * o beyond 62 bits, an unknown dtype.  At the launch: ceil(W o / base) of 2^30 or more. */
 int specinv_resample(const void* x, void* y, int64_t batch, int64_t n_in, int64_t n_out, int64_t orig_freq, int64_t new_freq,
                      int32_t lowpass_filter_width, double rolloff, int32_t dtype, int32_t device, void* hip_stream);
+/* Harmonic-percussive separation (not in the reference; csrc/kernels_hpss.h): librosa.decompose.hpss in one launch.  spec is
+ * (batch, n_freq, n_frames) on HIP device `device`, real non-negative magnitudes of `dtype` or, with is_complex != 0, (re, im) pairs
+ * of `dtype`; enqueued on hip_stream (NULL: the null stream).  No plan: nothing about an STFT is read and nothing is kept.
+ *     A = spec, or sqrt(re^2 + im^2) in float64 ;  refl(i, n) = j < n ? j : 2 n - 1 - j with j = i mod 2 n (>= 0) ;
+ *     harm[f, t] = median{ A[f, refl(t + d, T)] : |d| <= win_harm / 2 } ;  perc[f, t] = median{ A[refl(f + d, F), t] : |d| <= win_perc / 2 } ;
+ *     soft(X, R): power = inf: X > R ? 1 : 0 ; else Z = max(X, R) ; Z < tiny: (both margins 1 ? 0.5 : 0) ; else a = (X / Z)^power,
+ *     r = (R / Z)^power, a / (a + r) ;  M_h = soft(harm, margin_harm * perc) ;  M_p = soft(perc, margin_perc * harm) ;
+ * tiny is the smallest normal number of `dtype`.  The windows are odd, 1 ... 127, so a median is an element of its window (exact
+ * selection).  From Z on everything is float64 for both dtypes and the result is rounded once.  out_a, out_b by out_mode:
+ *     SPECINV_HPSS_COMPONENTS  spec * M_h, spec * M_p, of spec's kind (complex for a complex input) ;
+ *     SPECINV_HPSS_MASKS       M_h, M_p, real ;      SPECINV_HPSS_MEDIANS     harm, perc, real.
+ * Any batch: it is not a launch dimension of its own.  NaN input is unspecified.  Stateless: a running method is not disturbed.
+ * SPECINV_EINVAL, before the device is touched, in this order: a NULL pointer (spec, out_a, out_b) ; an output that is spec or the
+ * other output ; batch, n_freq or n_frames < 1 ; win_harm, then win_perc, even or outside 1 ... 127 ; power not > 0 (NaN included) ;
+ * margin_harm, then margin_perc, < 1 or not finite ; an unknown out_mode ; an unknown dtype. */
+enum { SPECINV_HPSS_COMPONENTS = 0, SPECINV_HPSS_MASKS = 1, SPECINV_HPSS_MEDIANS = 2 };
+int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames, int32_t win_harm,
+                 int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode, int32_t is_complex,
+                 int32_t dtype, int32_t device, void* hip_stream);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

@@ -25,4 +25,5 @@ from .constrained import constrained_griffin_lim, constrained_unfolded  # noqa: 
 from .projection import gla_projection, stft, istft                     # noqa: E402,F401
 from .timescale import phase_vocoder, time_stretch, stretched_frames, pitch_shift   # noqa: E402,F401
 from .resample import resample                                          # noqa: E402,F401
+from .hpss import hpss, hpss_medians, hpss_audio, harmonic, percussive   # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

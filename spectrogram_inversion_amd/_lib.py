@@ -18,6 +18,7 @@ PAD_MODES = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
 METRICS = {"SC": 0, "SNR": 1, "SER": 2}
 TF_MAG, TF_LOGMEL = 0, 1
 PVOC_LOCK = {None: 0, "identity": 1}
+HPSS_COMPONENTS, HPSS_MASKS, HPSS_MEDIANS = 0, 1, 2
 
 
 class StftCfg(C.Structure):
@@ -77,6 +78,8 @@ SIGNATURES = {
     "specinv_phase_vocoder": (C.c_int, [_P, _P, C.c_int32, _D, _P]),
     "specinv_phase_vocoder_locked": (C.c_int, [_P, _P, C.c_int32, _D, C.c_int32, _P]),
     "specinv_resample": (C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, C.c_int32, _D, C.c_int32, C.c_int32, _P]),
+    "specinv_hpss": (C.c_int, [_P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, _D, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_int32, _P]),
     "specinv_metric_sums": (C.c_int, [_P, _P, _P, _I64, _DP]),
     "specinv_gla_init": (C.c_int, [_P, _P, _P, _D]),
     "specinv_gla_iterate": (C.c_int, [_P, C.c_int, C.c_int, _DP]),

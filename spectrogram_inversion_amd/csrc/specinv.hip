@@ -6,6 +6,7 @@
 
 #include "kernels_mel_nnls.h"
 #include "kernels_mel_nnls_adjoint.h"
+#include "kernels_hpss.h"
 #include "kernels_resample.h"
 #include "plan_impl.h"
 
@@ -314,6 +315,36 @@ int specinv_resample(const void* x, void* y, int64_t batch, int64_t n_in, int64_
   if (dtype == SPECINV_F32)
     return resample_launch<float>((const float*)x, (float*)y, batch, n_in, n_out, o, n, lowpass_filter_width, rolloff, stream);
   return resample_launch<double>((const double*)x, (double*)y, batch, n_in, n_out, o, n, lowpass_filter_width, rolloff, stream);
+}
+int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames, int32_t win_harm,
+                 int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode, int32_t is_complex,
+                 int32_t dtype, int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec && out_a && out_b, SPECINV_EINVAL, "specinv_hpss: NULL %s", !spec ? "spec" : !out_a ? "out_a" : "out_b");
+  SI_CHECK(out_a != spec && out_b != spec && out_a != out_b, SPECINV_EINVAL, "specinv_hpss: %s",
+           out_a == out_b ? "out_b must not alias out_a" : "an output must not alias spec");
+  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
+           "specinv_hpss: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
+  SI_CHECK(win_harm >= 1 && win_harm <= kHpssMaxWin && (win_harm & 1), SPECINV_EINVAL,
+           "specinv_hpss: win_harm must be odd in 1 ... %d, got %d", kHpssMaxWin, win_harm);
+  SI_CHECK(win_perc >= 1 && win_perc <= kHpssMaxWin && (win_perc & 1), SPECINV_EINVAL,
+           "specinv_hpss: win_perc must be odd in 1 ... %d, got %d", kHpssMaxWin, win_perc);
+  SI_CHECK(power > 0, SPECINV_EINVAL, "specinv_hpss: power must be > 0 (inf included), got %g", power);
+  SI_CHECK(margin_harm >= 1 && std::isfinite(margin_harm), SPECINV_EINVAL, "specinv_hpss: margin_harm must be finite and >= 1, got %g",
+           margin_harm);
+  SI_CHECK(margin_perc >= 1 && std::isfinite(margin_perc), SPECINV_EINVAL, "specinv_hpss: margin_perc must be finite and >= 1, got %g",
+           margin_perc);
+  SI_CHECK(out_mode == SPECINV_HPSS_COMPONENTS || out_mode == SPECINV_HPSS_MASKS || out_mode == SPECINV_HPSS_MEDIANS, SPECINV_EINVAL,
+           "specinv_hpss: out_mode must be SPECINV_HPSS_COMPONENTS, _MASKS or _MEDIANS, got %d", out_mode);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (dtype == SPECINV_F32)
+    return hpss_launch<float>((const float*)spec, (float*)out_a, (float*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
+                              margin_harm, margin_perc, out_mode, is_complex != 0, stream);
+  return hpss_launch<double>((const double*)spec, (double*)out_a, (double*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
+                             margin_harm, margin_perc, out_mode, is_complex != 0, stream);
 }
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]) {
   ENTER(plan);
