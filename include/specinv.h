@@ -246,12 +246,12 @@ int specinv_agla_init(specinv_plan* plan, const void* init_spec, const void* mag
  * a NULL array, an alpha or beta entry < 0, a gamma entry <= 0, a NULL plan. */
 int specinv_agla_init_sched(specinv_plan* plan, const void* init_spec, const void* mag, int n_sched, const double* alpha,
                             const double* beta, const double* gamma);
-/* Known bins and known samples for the iterations that follow (constrained_griffin_lim; csrc/kernels_cgla.h).  With M the mask of
+/* Known bins and known samples for the iterations that follow (constrained_griffin_lim; csrc/kernels_agla.h).  With M the mask of
  * known bins and K their values, the host layer passes mag = where(M, 0, m) to specinv_agla_init and here
  *     offset = where(W, xk, ISTFT(where(M, K, 0))),  (batch, length) in the plan's dtype,
  *     fixed_mask = W, (batch, length) uint8, non-zero where the sample xk is known - or NULL: no sample is.
  * Both are device arrays; the plan keeps copies (device_bytes grows by batch * length * (sizeof(T) [+ 1])).  Every iteration then
- * runs k_cgla_step for k_agla_step:  u = y + offset;  t_n = where(W, offset, (1 - gamma) d_{n-1} + gamma u);  c_n and d_n as above;
+ * runs the constrained form of k_agla_step:  u = y + offset;  t_n = where(W, offset, (1 - gamma) d_{n-1} + gamma u);  c_n and d_n as above;
  * t, c and d hold xk bit for bit under W.  Both NULL clears the constraint, and so does every specinv_*_init.  An evaluating
  * iteration's sums compare against mag, zeros under M: evaluate |STFT(t_n)| against the full target instead (specinv_stft,
  * specinv_metric_sums).  SPECINV_ESTATE: the plan is not in the AGLA state (call after specinv_agla_init / _init_sched).
@@ -328,7 +328,7 @@ int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t
  * to the start. */
 int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
                                void* gmag_fm_accum);
-/* the backward sweep of constrained_unfolded (csrc/kernels_cgla_adjoint.h): the three entries above under the constraint of
+/* the backward sweep of constrained_unfolded (csrc/kernels_agla_adjoint.h): the three entries above under the constraint of
  * specinv_agla_constrain, in their argument order and with their error rules.  fixed_mask is W, (batch, length) uint8, non-zero where
  * the sample is known, or NULL: no sample is.  goff_accum (batch, length) accumulates the cotangent of offset = where(W, xk, k).
  * Iteration n >= 2 is t_n = where(W, offset, (1 - gamma_n) d_{n-1} + gamma_n (P(c_{n-1}) + offset)); with s as above and

@@ -113,6 +113,50 @@ def _schedule(name, value, n_iter):
     return t.expand(n_iter)
 
 
+def _schedules(n_iter, alpha, beta, gamma):
+    """The checked `n_iter` and parameters of an unfolded layer: alpha, beta (None: alpha), gamma as (n_iter,) float64 CPU tensors
+    and their values as three lists."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 1:
+        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
+    al = _schedule("alpha", alpha, n_iter)
+    be = al if beta is None else _schedule("beta", beta, n_iter)
+    ga = _schedule("gamma", gamma, n_iter)
+    sched = [t.detach().tolist() for t in (al, be, ga)]
+    if not all(v >= 0 for v in sched[0] + sched[1]):
+        raise ValueError(f"alpha and beta must be >= 0, got {sched[0]} and {sched[1]}")
+    if not all(v > 0 for v in sched[2]):
+        raise ValueError(f"gamma must be > 0, got {sched[2]}")
+    return al, be, ga, sched
+
+
+def _sweep(plan, t, sched, g_y, mag_fm, fixed_mask=None, goff=None):
+    """The backward sweep of an unfolded layer over the recorded signals t[0] = c_0, t[n] = t_n: one `specinv_agla_step_adjoint`
+    for n = N ... 2, the closing step and the ISTFT's adjoint.  With `goff` (batch, length), which gains the cotangent of the
+    constraint's offset, the constrained sweep (`specinv_cgla_*`) under the bool mask `fixed_mask` of known samples, or None.
+    Returns the cotangent of the start's spectrogram, of the frame-major magnitudes `mag_fm` and the (N, 3) gradients of alpha_n,
+    beta_n, gamma_n on the device."""
+    al, be, ga = sched
+    n_iter = len(al)
+    gm_fm = torch.zeros_like(mag_fm)
+    a = g_y.detach().to(plan.dtype).clone(memory_format=torch.contiguous_format)   # (the sweep works in place)
+    gc = torch.zeros_like(a)
+    gd = torch.zeros_like(a) if any(g != 1.0 for g in ga) else None                # (every gamma = 1: gd stays 0)
+    c_prev = torch.empty_like(a)
+    dots = torch.zeros((n_iter, 3), dtype=torch.float64, device=plan.device)       # row 0: iteration 1 does not extrapolate
+    w8 = None if fixed_mask is None else fixed_mask.to(torch.uint8)                # (the kernel's form of the mask, once)
+    for n in range(n_iter, 1, -1):
+        step = (t[n], t[n - 1], t[n - 2] if n > 2 else None, (al[n - 1], be[n - 1], ga[n - 1], al[n - 2], be[n - 2]))
+        if goff is None:
+            plan.agla_step_adjoint(*step, a, gc, gd, c_prev, dots[n - 1], mag_fm, gm_fm)
+        else:
+            plan.cgla_step_adjoint(*step, w8, a, gc, gd, goff, c_prev, dots[n - 1], mag_fm, gm_fm)
+    if goff is None:
+        plan.agla_first_adjoint(t[0], a, gc, gd, mag_fm, gm_fm)
+    else:
+        plan.cgla_first_adjoint(t[0], w8, a, gc, gd, goff, mag_fm, gm_fm)
+    return plan.istft_adjoint(gc), gm_fm, dots
+
+
 class _AglaUnfoldedFn(torch.autograd.Function):
     """`n_iter` AGLA iterations as one differentiable layer.  The forward pass is the inference kernels with c_0 = ISTFT(start) and
     t_1 ... t_N recorded, (N + 1) B L reals; the backward sweep recomputes c_{n-1} and d_{n-1} from the t's and runs one
@@ -142,21 +186,9 @@ class _AglaUnfoldedFn(torch.autograd.Function):
         plan = ctx.plan
         start, y, *t = ctx.saved_tensors
         t.append(y)                                                # t[0] = c_0, t[n] = t_n
-        al, be, ga = ctx.sched
-        n_iter = len(al)
         mag = start if ctx.real_in else start.abs()
         mag_fm = mag.transpose(1, 2).contiguous()                  # frame-major once, not once per iteration
-        gm_fm = torch.zeros_like(mag_fm)
-        a = g_y.detach().to(plan.dtype).clone(memory_format=torch.contiguous_format)   # (the sweep works in place)
-        gc = torch.zeros_like(a)
-        gd = torch.zeros_like(a) if any(g != 1.0 for g in ga) else None                # (every gamma = 1: gd stays 0)
-        c_prev = torch.empty_like(a)
-        dots = torch.zeros((n_iter, 3), dtype=torch.float64, device=plan.device)       # row 0: iteration 1 does not extrapolate
-        for n in range(n_iter, 1, -1):
-            coef = (al[n - 1], be[n - 1], ga[n - 1], al[n - 2], be[n - 2])
-            plan.agla_step_adjoint(t[n], t[n - 1], t[n - 2] if n > 2 else None, coef, a, gc, gd, c_prev, dots[n - 1], mag_fm, gm_fm)
-        plan.agla_first_adjoint(t[0], a, gc, gd, mag_fm, gm_fm)
-        g_c0 = plan.istft_adjoint(gc)
+        g_c0, gm_fm, dots = _sweep(plan, t, ctx.sched, g_y, mag_fm)
         g_spec = _input_grad(ctx, plan, mag, start, g_c0, gm_fm.transpose(1, 2).contiguous())
         g_par = dots.cpu() if any(ctx.needs_input_grad[1:4]) else None
         return (g_spec, *(g_par[:, k] if ctx.needs_input_grad[1 + k] else None for k in range(3)), None, None)
@@ -179,16 +211,7 @@ def agla_unfolded(spec, n_iter=5, alpha=0.99, beta=None, gamma=1.0, **stft_kwarg
         raise TypeError("spec must be a torch.Tensor")
     if spec.dim() not in (2, 3):
         raise ValueError(f"spec must be (F, T) or (B, F, T), got shape {tuple(spec.shape)}")
-    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 1:
-        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
-    al = _schedule("alpha", alpha, n_iter)
-    be = al if beta is None else _schedule("beta", beta, n_iter)
-    ga = _schedule("gamma", gamma, n_iter)
-    sched = [t.detach().tolist() for t in (al, be, ga)]
-    if not all(v >= 0 for v in sched[0] + sched[1]):
-        raise ValueError(f"alpha and beta must be >= 0, got {sched[0]} and {sched[1]}")
-    if not all(v > 0 for v in sched[2]):
-        raise ValueError(f"gamma must be > 0, got {sched[2]}")
+    al, be, ga, sched = _schedules(n_iter, alpha, beta, gamma)
     spec3, args, rdtype, half = _prepare(spec, stft_kwargs)
     if spec3.shape[0] > _MAX_PLAN_BATCH:
         raise ValueError(f"spec of shape {tuple(spec.shape)} holds {spec3.shape[0]} items, agla_unfolded takes at most {_MAX_PLAN_BATCH}")

@@ -9,8 +9,8 @@ Y = where(M, K, S m / (|S| + 1e-16)) followed by the ISTFT is, the STFT being li
 
 the projection launch of `accelerated_griffin_lim` with zeros in its magnitude operand, plus a constant signal made once.  A known
 sample is one more select on the same (B, L) signal.  An iteration stays the projection launch plus one launch over the samples
-(`specinv_agla_constrain`, csrc/kernels_cgla.h); no state of the spectrogram's size exists.  `constrained_unfolded` is a fixed
-number of these iterations as a differentiable layer (csrc/kernels_cgla_adjoint.h).  Not part of the reference's surface.
+(`specinv_agla_constrain`, csrc/kernels_agla.h); no state of the spectrogram's size exists.  `constrained_unfolded` is a fixed
+number of these iterations as a differentiable layer (csrc/kernels_agla_adjoint.h).  Not part of the reference's surface.
 """
 from __future__ import annotations
 
@@ -19,7 +19,7 @@ from tqdm import tqdm
 
 from . import _lib
 from . import methods as _m
-from .agla import _finish, _prepare, _schedule, accelerated_griffin_lim, agla_unfolded
+from .agla import _finish, _prepare, _schedules, _sweep, accelerated_griffin_lim, agla_unfolded
 from .autograd import _input_grad
 from .metrics import _from_sums
 from .plan import get_plan, require_gpu, trim_plan_cache
@@ -182,7 +182,7 @@ def constrained_griffin_lim(spec, known_spec=None, spec_mask=None, known_wave=No
 class _CglaUnfoldedFn(torch.autograd.Function):
     """`n_iter` constrained AGLA iterations as one differentiable layer, `_AglaUnfoldedFn` under the constraint.  The forward pass is
     the inference kernels with c_0 = ISTFT(start) and t_1 ... t_N recorded, (N + 1) B L reals; the backward sweep runs one
-    `specinv_cgla_step_adjoint` per iteration (csrc/kernels_cgla_adjoint.h), which also accumulates the cotangent of the constant
+    `specinv_cgla_step_adjoint` per iteration (csrc/kernels_agla_adjoint.h), which also accumulates the cotangent of the constant
     signal where(W, xk, k), and splits that and the start's between `spec`, `known_spec` and `known_wave` once at the end."""
 
     @staticmethod
@@ -208,27 +208,14 @@ class _CglaUnfoldedFn(torch.autograd.Function):
         start, y, *t = ctx.saved_tensors
         K = t.pop() if ctx.has_K else None
         t.append(y)                                                # t[0] = c_0, t[n] = t_n
-        al, be, ga = ctx.sched
-        n_iter = len(al)
         m = start if ctx.real_in else start.abs()
         m_full, m_free = m, m
         if K is not None:
             absK = K.abs()
             m_full, m_free = torch.where(M, absK, m), torch.where(M, torch.zeros_like(m), m)
         mag_fm = m_free.transpose(1, 2).contiguous()               # frame-major once, not once per iteration
-        gm_fm = torch.zeros_like(mag_fm)
-        a = g_y.detach().to(plan.dtype).clone(memory_format=torch.contiguous_format)   # (the sweep works in place)
-        gc, goff = torch.zeros_like(a), torch.zeros_like(a)
-        gd = torch.zeros_like(a) if any(g != 1.0 for g in ga) else None                # (every gamma = 1: gd stays 0)
-        c_prev = torch.empty_like(a)
-        dots = torch.zeros((n_iter, 3), dtype=torch.float64, device=plan.device)       # row 0: iteration 1 does not extrapolate
-        w8 = None if W is None else W.to(torch.uint8)              # (the kernel's form of the mask, once)
-        for n in range(n_iter, 1, -1):
-            coef = (al[n - 1], be[n - 1], ga[n - 1], al[n - 2], be[n - 2])
-            plan.cgla_step_adjoint(t[n], t[n - 1], t[n - 2] if n > 2 else None, coef, w8, a, gc, gd, goff, c_prev, dots[n - 1],
-                                   mag_fm, gm_fm)
-        plan.cgla_first_adjoint(t[0], w8, a, gc, gd, goff, mag_fm, gm_fm)
-        g_start = plan.istft_adjoint(gc)
+        goff = torch.zeros((plan.batch, plan.length), dtype=plan.dtype, device=plan.device)
+        g_start, gm_fm, dots = _sweep(plan, t, ctx.sched, g_y, mag_fm, W, goff)
         gm = gm_fm.transpose(1, 2).contiguous()
         g_xk = None if W is None else torch.where(W, goff, torch.zeros_like(goff))
         g_K = None
@@ -279,16 +266,7 @@ def constrained_unfolded(spec, known_spec=None, spec_mask=None, known_wave=None,
         spec_mask = _expanded("known_spec", known_spec, "spec_mask", spec_mask, spec.shape)
     if not has_spec and not has_wave:
         return agla_unfolded(spec, n_iter=n_iter, alpha=alpha, beta=beta, gamma=gamma, **stft_kwargs)
-    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 1:
-        raise ValueError(f"n_iter must be an integer >= 1, got {n_iter!r}")
-    al = _schedule("alpha", alpha, n_iter)
-    be = al if beta is None else _schedule("beta", beta, n_iter)
-    ga = _schedule("gamma", gamma, n_iter)
-    sched = [t.detach().tolist() for t in (al, be, ga)]
-    if not all(v >= 0 for v in sched[0] + sched[1]):
-        raise ValueError(f"alpha and beta must be >= 0, got {sched[0]} and {sched[1]}")
-    if not all(v > 0 for v in sched[2]):
-        raise ValueError(f"gamma must be > 0, got {sched[2]}")
+    al, be, ga, sched = _schedules(n_iter, alpha, beta, gamma)
     spec3, args, rdtype, half = _prepare(spec, stft_kwargs)
     batch, _, n_frames = spec3.shape
     length = args.signal_length(n_frames)

@@ -11,9 +11,19 @@
 // Memory-bound on plain rows: ten transfers of sizeof(T) per sample (a, gc, gd, t_n, t_{n-1}, t_{n-2} read; a, gc, gd, c_prev
 // written), eight with every gamma = 1, where gd is identically 0 and neither allocated nor touched; the envelope's L values stay in
 // the caches.
+//
+// Under a constraint (constrained_unfolded) iteration n >= 2 is
+//     u = P(c_{n-1}) + off ;  t_n = where(W, off, (1 - gamma_n) d_{n-1} + gamma_n u) ;  c_n, d_n as above,
+// off = where(W, xk, k) the one constant signal of the run, and the sweep also carries goff, the cotangent of off, which it
+// accumulates.  With s' = W ? 0 : s, what passes the select:
+//     gamma_bar_n = <s', t_n - d_{n-1}> / gamma_n ;  goff += W ? s : gamma_n s' ;  gd <- (1 - gamma_n) s' ;  gc <- gamma_n s' / env
+// and alpha_bar_n, beta_bar_n, a and c_prev as above.  Off W, t_n - d_{n-1} = gamma_n (u - d_{n-1}); on W, s' is 0: no u has to be
+// recorded.  gc then goes through the projection adjoint at c_prev against m' = where(M, 0, m).  FIRST, t_1 = c_1 = d_1 =
+// where(W, off, P(c_0) + off):  s = a + gc + gd ;  goff += s ;  gc <- s' / env.  goff read and written and one mask byte per sample
+// beside the transfers above.
 #pragma once
 #include "common.h"
-#include "kernels_misi.h"
+#include "kernels_agla.h"
 
 namespace specinv {
 
@@ -36,6 +46,9 @@ struct AglaAdjArgs {
   int64_t upr;       // work items per row: L / V
   int64_t n_units;   // B * upr
   int first;         // the closing step
+  // the constraint, read by the CONSTRAINED kernel alone (last: the other kernels see the fields above where they were)
+  T* goff;               // (B, L): the cotangent of off, accumulated; nullptr: no constraint
+  const uint8_t* mask;   // (B, L): non-zero where the sample is known; nullptr: no sample is
 };
 
 // V: consecutive samples per thread, one load / store of V * sizeof(T) bytes each (rows start at multiples of L elements, L % V == 0
@@ -43,7 +56,9 @@ struct AglaAdjArgs {
 // it.  The inner products: every factor converted to double (delta and t_n - d_{n-1} are formed there from the recorded values),
 // multiplied and accumulated in double per thread, summed over the wave by data-parallel-primitive moves (wave_scan_inclusive: lane
 // 63 holds the total), over the four waves through LDS in a fixed order - no atomics, one triple per workgroup.
-template <typename T, int V, bool GENERAL>
+// CONSTRAINED: goff and the mask are read beside the cotangents, the V mask bytes of a thread in one load; the mask pointer is
+// uniform, one scalar branch per work item.  Every element of goff is written by the thread that read it.
+template <typename T, int V, bool GENERAL, bool CONSTRAINED>
 __global__ void __launch_bounds__(256) k_agla_step_adjoint(AglaAdjArgs<T> p) {
   using Vec = MisiVec<T, V>;
   __shared__ double red[3][4];
@@ -57,16 +72,28 @@ __global__ void __launch_bounds__(256) k_agla_step_adjoint(AglaAdjArgs<T> p) {
     const Vec e = *reinterpret_cast<const Vec*>(p.env + n);
     const Vec a = *reinterpret_cast<const Vec*>(p.a + at);
     Vec gc = *reinterpret_cast<const Vec*>(p.gc + at);
+    Vec go{};
+    if constexpr (CONSTRAINED) go = *reinterpret_cast<const Vec*>(p.goff + at);
     Vec gd{};
     if constexpr (GENERAL) gd = *reinterpret_cast<const Vec*>(p.gd + at);
+    CglaMask<V> w{};
+    if constexpr (CONSTRAINED) {
+      if (p.mask != nullptr) w = *reinterpret_cast<const CglaMask<V>*>(p.mask + at);
+    }
     if (p.first) {
 #pragma unroll
       for (int i = 0; i < V; ++i) {
         T s = a.v[i] + gc.v[i];
         if constexpr (GENERAL) s += gd.v[i];
-        gc.v[i] = s / e.v[i];
+        if constexpr (CONSTRAINED) {
+          go.v[i] += s;
+          gc.v[i] = w.v[i] ? T(0) : s / e.v[i];
+        } else {
+          gc.v[i] = s / e.v[i];
+        }
       }
       *reinterpret_cast<Vec*>(p.gc + at) = gc;
+      if constexpr (CONSTRAINED) *reinterpret_cast<Vec*>(p.goff + at) = go;
       continue;
     }
     const Vec tn = *reinterpret_cast<const Vec*>(p.tn + at);
@@ -93,14 +120,24 @@ __global__ void __launch_bounds__(256) k_agla_step_adjoint(AglaAdjArgs<T> p) {
         s += one_b * gd.v[i];
         an.v[i] -= p.beta * gd.v[i];
         s_be += (double)gd.v[i] * delta;
-        gdn.v[i] = p.one_minus_gamma * s;
       }
-      s_ga += (double)s * ((double)tn.v[i] - dprev[i]);
-      gc.v[i] = GENERAL ? p.gamma * s / e.v[i] : s / e.v[i];
+      if constexpr (CONSTRAINED) {
+        const T sp = w.v[i] ? T(0) : s;                              // s'
+        if constexpr (GENERAL) gdn.v[i] = p.one_minus_gamma * sp;
+        s_ga += (double)sp * ((double)tn.v[i] - dprev[i]);
+        const T through = GENERAL ? p.gamma * sp : sp;               // to u: to the projection and, off W, to off
+        go.v[i] += w.v[i] ? s : through;
+        gc.v[i] = through / e.v[i];
+      } else {
+        if constexpr (GENERAL) gdn.v[i] = p.one_minus_gamma * s;
+        s_ga += (double)s * ((double)tn.v[i] - dprev[i]);
+        gc.v[i] = GENERAL ? p.gamma * s / e.v[i] : s / e.v[i];
+      }
     }
     *reinterpret_cast<Vec*>(p.a + at) = an;
     *reinterpret_cast<Vec*>(p.gc + at) = gc;
     if constexpr (GENERAL) *reinterpret_cast<Vec*>(p.gd + at) = gdn;
+    if constexpr (CONSTRAINED) *reinterpret_cast<Vec*>(p.goff + at) = go;
     *reinterpret_cast<Vec*>(p.c_prev + at) = cp;
   }
   if (p.first) return;
@@ -122,14 +159,11 @@ __global__ void __launch_bounds__(256) k_agla_step_adjoint(AglaAdjArgs<T> p) {
 }
 
 // Host side (tu_agla_adjoint.hip): picks V (the widest of 16 / 8 / 4 bytes - float64: 16 / 8 - that divides L and the pointers'
-// alignment) and GENERAL (p.gd != nullptr), launches at most kAglaAdjMaxGrid workgroups of 256 and, unless p.first, the finishing
-// launch (k_agla_dots_finish, one workgroup that sums the partial triples in a fixed order) that leaves {alpha_bar, beta_bar,
-// gamma_bar} in dots_dev (3 doubles on the device; beta_bar = 0 without gd).  p.upr and p.n_units are filled in here; p.partials
-// holds 3 * kAglaAdjMaxGrid doubles.
+// alignment), GENERAL (p.gd != nullptr) and CONSTRAINED (p.goff != nullptr), launches at most kAglaAdjMaxGrid workgroups of 256
+// and, unless p.first, the finishing launch (k_agla_dots_finish, one workgroup that sums the partial triples in a fixed order) that
+// leaves {alpha_bar, beta_bar, gamma_bar} in dots_dev (3 doubles on the device; beta_bar = 0 without gd).  p.upr and p.n_units are
+// filled in here; p.partials holds 3 * kAglaAdjMaxGrid doubles.
 template <typename T>
 int agla_step_adjoint_launch(AglaAdjArgs<T> p, int batch, double* dots_dev, hipStream_t stream);
-
-// The finishing launch alone, for the sweeps that share it (kernels_cgla_adjoint.h): n_part partial triples -> dots_dev.
-int agla_dots_finish_launch(const double* partials, int n_part, double gamma, double* dots_dev, hipStream_t stream);
 
 }  // namespace specinv

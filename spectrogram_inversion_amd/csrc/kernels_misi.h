@@ -5,6 +5,8 @@
 // Memory-bound: (2 K + 1) sizeof(T) bytes per mixture sample (K = 2, 3, 4 keep the K values in registers: one read, one write per
 // source; larger K reads the sources twice, 3 K + 1).
 #pragma once
+#include <initializer_list>
+
 #include "common.h"
 #include "fast_core.h"
 
@@ -30,6 +32,19 @@ template <typename T, int V>
 struct alignas(sizeof(T) * V) MisiVec {
   T v[V];
 };
+
+// Host side, the V a launcher takes: the widest of 16 / 8 / 4 bytes (float64: 16 / 8) in samples that divides L, the hop where the
+// rows have chunk tails (hop = 0: none) and the address of every pointer in `rows` - every row starts at a multiple of L (hop)
+// elements from its base.  `bytes` is an array of one byte per sample (a mask): V bytes per thread.  nullptr is aligned.
+template <typename T>
+inline int misi_vec_width(int64_t L, int hop, std::initializer_list<const void*> rows, const void* bytes = nullptr) {
+  for (int v = sizeof(T) == 4 ? 4 : 2; v > 1; v /= 2) {
+    bool ok = L % v == 0 && hop % v == 0 && reinterpret_cast<uintptr_t>(bytes) % v == 0;
+    for (const void* p : rows) ok = ok && reinterpret_cast<uintptr_t>(p) % (v * sizeof(T)) == 0;
+    if (ok) return v;
+  }
+  return 1;
+}
 
 // Offset of the tail samples that belong to samples n ... n + V - 1 of a row (hop % V == 0, n % V == 0: one hop-block) inside the
 // row's nchunks * nb * hop tail entries, -1 where the row's x is the whole value

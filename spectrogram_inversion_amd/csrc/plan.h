@@ -54,7 +54,7 @@ struct PlanBase {
   // (a schedule: iteration n takes entry min(n, n_sched) - 1 of the three host arrays)
   virtual int agla_init_sched(const void* init_spec, const void* mag, int n_sched, const double* alpha, const double* beta,
                               const double* gamma) = 0;
-  // ... under known bins and known samples for the iterations that follow (kernels_cgla.h); both nullptr: no constraint
+  // ... under known bins and known samples for the iterations that follow (kernels_agla.h); both nullptr: no constraint
   virtual int agla_constrain(const void* offset, const void* fixed_mask) = 0;
   virtual int iterate(int n_iter, bool eval_last, double sums[4]) = 0;
   // evaluations whose result cannot influence the run (tol == 0, no callback) stay on the device and are
@@ -81,22 +81,16 @@ struct PlanBase {
   // MISI's backward sweep (kernels_misi_adjoint.h): the coupling step's adjoint, and one whole unfolded iteration's; stateless
   virtual int misi_mix_adjoint(int n_src, void* g, void* gmix) = 0;
   virtual int misi_step_adjoint(int n_src, const void* x_prev, const void* mag_fm, void* g, void* gmix, void* gmag_fm) = 0;
-  // AGLA's backward sweep (kernels_agla_adjoint.h): the extrapolation's adjoint alone, with the projection's, the closing step;
-  // stateless
+  // AGLA's backward sweep (kernels_agla_adjoint.h): the extrapolation's adjoint alone, with the projection's, the closing step.
+  // goff != nullptr: constrained AGLA's, with the sample mask (nullptr: no known sample) and goff, the accumulated cotangent of the
+  // constraint's offset; stateless
   virtual int agla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
-                                  void* gd, void* c_prev, void* dots_dev) = 0;
+                                  void* gd, void* c_prev, void* dots_dev, const void* fixed_mask, void* goff) = 0;
   virtual int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc,
-                                void* gd, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) = 0;
-  virtual int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) = 0;
-  // constrained AGLA's backward sweep (kernels_cgla_adjoint.h): the same three with the sample mask (nullptr: no known sample) and
-  // goff, the accumulated cotangent of the constraint's offset; stateless
-  virtual int cgla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask,
-                                  void* a, void* gc, void* gd, void* goff, void* c_prev, void* dots_dev) = 0;
-  virtual int cgla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask,
-                                void* a, void* gc, void* gd, void* goff, void* c_prev, void* dots_dev, const void* mag_fm,
-                                void* gmag_fm) = 0;
-  virtual int cgla_first_adjoint(const void* c0, const void* fixed_mask, const void* a, void* gc, const void* gd, void* goff,
-                                 const void* mag_fm, void* gmag_fm) = 0;
+                                void* gd, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm, const void* fixed_mask,
+                                void* goff) = 0;
+  virtual int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm,
+                                 const void* fixed_mask, void* goff) = 0;
   // gla_projection: y = ISTFT(m S / (|S| + 1e-16)), S = STFT(x), and its adjoint - one fused launch where
   // project_adjoint_kind() is 1, else the stages of the sweeps above; stateless
   virtual int project(const void* x, const void* mag_fm, void* y_out) = 0;

@@ -20,8 +20,6 @@
 #include "kernels_agla.h"
 #include "kernels_misi_adjoint.h"
 #include "kernels_agla_adjoint.h"
-#include "kernels_cgla.h"
-#include "kernels_cgla_adjoint.h"
 #include "kernels_pvoc.h"
 #include "kernels_pvoc_lock.h"
 #include "proj_adjoint_api.h"
@@ -115,7 +113,7 @@ struct PlanT final : PlanBase {
   DevBuf agla_adj_part;                 // agla_*_adjoint: the workgroups' partial inner products
   int64_t agla_n = 0;                   // ... iterations since agla_init (0: t holds nothing yet)
   DevBuf pvoc_phi;                      // phase_vocoder_locked: the running phase as float64, (batch, n_freq, frames)
-  DevBuf cgla_off, cgla_mask;           // agla_constrain: where(W, xk, k) and W, (batch, length) each (kernels_cgla.h); no p: none set
+  DevBuf cgla_off, cgla_mask;           // agla_constrain: where(W, xk, k) and W, (batch, length) each (kernels_agla.h); no p: none set
   bool proj_adj_fused = false;          // project_adjoint: k_wave_proj_adjoint (kernels_proj_adjoint.h) instead of the stages
   int proj_adj_max_waves = 0;           // ... SPECINV_PROJ_ADJ_WAVES: at most so many waves per launch (0: the chip's fill)
   FastState<T> fast;
@@ -735,8 +733,8 @@ struct PlanT final : PlanBase {
     return launch_mix();
   }
 
-  // The state the next projection launch reads, for a kernel that edits it between two launches (MisiMixArgs, AglaStepArgs,
-  // CglaStepArgs): the plan's x on the coverage kernels (after the overlap-add, after the swap of the register / ring form);
+  // The state the next projection launch reads, for a kernel that edits it between two launches (MisiMixArgs,
+  // AglaStepArgs): the plan's x on the coverage kernels (after the overlap-add, after the swap of the register / ring form);
   // xb[cur] on the float32 wave-level kernels, whose fused forms keep the chunk tails beside it.
   template <typename Args>
   void signal_state(Args& a) {
@@ -791,7 +789,7 @@ struct PlanT final : PlanBase {
     return SPECINV_OK;
   }
 
-  // Known bins and known samples for the iterations that follow (kernels_cgla.h): offset = where(W, xk, k) (batch, length) in the
+  // Known bins and known samples for the iterations that follow (kernels_agla.h): offset = where(W, xk, k) (batch, length) in the
   // plan's dtype, fixed_mask = W as bytes or nullptr; both nullptr: none.  The plan keeps copies, as MISI keeps its mixture.
   int agla_constrain(const void* offset, const void* fixed_mask) override {
     SI_CHECK(method == Method::Agla, SPECINV_ESTATE, "specinv_agla_init has not been called");
@@ -813,28 +811,10 @@ struct PlanT final : PlanBase {
     return SPECINV_OK;
   }
 
-  // The extrapolation on the state the projection launch has just written and the next one reads (launch_mix's contract)
+  // The extrapolation on the state the projection launch has just written and the next one reads (launch_mix's contract); under a
+  // constraint the offset and the mask are read beside it
   int launch_agla() {
-    if (cgla_off.p != nullptr) return launch_cgla();
     AglaStepArgs<T> a{};
-    signal_state(a);
-    a.t = agla_t.as<T>();
-    a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
-    const AglaCoef& k = agla_sched[(size_t)std::min<int64_t>(agla_n, (int64_t)agla_sched.size() - 1)];   // iteration agla_n + 1
-    a.alpha = k.alpha;
-    a.beta = k.beta;
-    a.gamma = k.gamma;
-    a.one_minus_gamma = k.omg;
-    a.L = length;
-    a.first = agla_n == 0 ? 1 : 0;
-    SI_TRY(agla_step_launch<T>(a, B(), stream));
-    ++agla_n;
-    return SPECINV_OK;
-  }
-
-  // ... under a constraint: k_cgla_step, the same contract with the offset and the mask read beside it
-  int launch_cgla() {
-    CglaStepArgs<T> a{};
     signal_state(a);
     a.t = agla_t.as<T>();
     a.d = agla_general ? agla_d.as<T>() : (T*)nullptr;
@@ -847,7 +827,7 @@ struct PlanT final : PlanBase {
     a.one_minus_gamma = k.omg;
     a.L = length;
     a.first = agla_n == 0 ? 1 : 0;
-    SI_TRY(cgla_step_launch<T>(a, B(), stream));
+    SI_TRY(agla_step_launch<T>(a, B(), stream));
     ++agla_n;
     return SPECINV_OK;
   }
@@ -1196,114 +1176,67 @@ struct PlanT final : PlanBase {
     return grad_from_spec(tmp_spec.as<C>(), u, fc.fwd_scale, length);                                // A^T
   }
 
-  // The adjoint of AGLA's extrapolation step n >= 2 (kernels_agla_adjoint.h); coef = {alpha_n, beta_n, gamma_n, alpha_{n-1},
-  // beta_{n-1}}, each rounded to T once.  Only agla_adj_part is written beside the caller's arrays.
+  // The arguments of k_agla_step_adjoint for step n >= 2; coef = {alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1}}, each rounded
+  // to T once.  coef == nullptr: the closing step, which reads a, gc, gd (and the constraint) alone.
+  AglaAdjArgs<T> agla_adj_args(const void* t_n, const void* t_nm1, const void* t_nm2, const double* coef, const void* a, void* gc,
+                               const void* gd, void* c_prev, const void* fixed_mask, void* goff) {
+    AglaAdjArgs<T> p{};
+    p.a = const_cast<T*>(static_cast<const T*>(a));
+    p.gc = static_cast<T*>(gc);
+    p.gd = const_cast<T*>(static_cast<const T*>(gd));
+    p.tn = static_cast<const T*>(t_n);
+    p.tp = static_cast<const T*>(t_nm1);
+    p.tpp = static_cast<const T*>(t_nm2);
+    p.env = env.as<T>();
+    p.c_prev = static_cast<T*>(c_prev);
+    p.mask = static_cast<const uint8_t*>(fixed_mask);
+    p.goff = static_cast<T*>(goff);
+    p.L = length;
+    p.first = coef == nullptr ? 1 : 0;
+    if (coef != nullptr) {
+      p.partials = agla_adj_part.as<double>();
+      p.alpha = (T)coef[0];
+      p.beta = (T)coef[1];
+      p.gamma = (T)coef[2];
+      p.one_minus_gamma = (T)(1.0 - coef[2]);
+      p.alpha_p = (T)coef[3];
+      p.beta_p = (T)coef[4];
+    }
+    return p;
+  }
+
+  // The adjoint of AGLA's extrapolation step n >= 2 (kernels_agla_adjoint.h).  goff != nullptr: under a constraint, with the sample
+  // mask (nullptr: no known sample) and goff, which it accumulates.  Only agla_adj_part is written beside the caller's arrays.
   int agla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc, void* gd,
-                          void* c_prev, void* dots_dev) override {
-    SI_CHECK(t_n && t_nm1 && coef && a && gc && c_prev && dots_dev, SPECINV_EINVAL, "null pointer");
+                          void* c_prev, void* dots_dev, const void* fixed_mask, void* goff) override {
+    SI_CHECK(t_n && t_nm1 && coef && a && gc && c_prev && dots_dev && (goff || !fixed_mask), SPECINV_EINVAL, "null pointer");
     SI_CHECK(coef[0] >= 0 && coef[1] >= 0 && coef[3] >= 0 && coef[4] >= 0 && coef[2] > 0, SPECINV_EINVAL,
              "alpha and beta must be >= 0, gamma > 0");
     SI_CHECK(gd != nullptr || coef[2] == 1.0, SPECINV_EINVAL, "gamma = %g needs gd", coef[2]);
     SI_TRY(agla_adj_part.reserve((size_t)3 * kAglaAdjMaxGrid * sizeof(double)));
-    AglaAdjArgs<T> p{};
-    p.a = static_cast<T*>(a);
-    p.gc = static_cast<T*>(gc);
-    p.gd = static_cast<T*>(gd);
-    p.tn = static_cast<const T*>(t_n);
-    p.tp = static_cast<const T*>(t_nm1);
-    p.tpp = static_cast<const T*>(t_nm2);
-    p.env = env.as<T>();
-    p.c_prev = static_cast<T*>(c_prev);
-    p.partials = agla_adj_part.as<double>();
-    p.alpha = (T)coef[0];
-    p.beta = (T)coef[1];
-    p.gamma = (T)coef[2];
-    p.one_minus_gamma = (T)(1.0 - coef[2]);
-    p.alpha_p = (T)coef[3];
-    p.beta_p = (T)coef[4];
-    p.L = length;
-    return agla_step_adjoint_launch<T>(p, B(), static_cast<double*>(dots_dev), stream);
+    return agla_step_adjoint_launch<T>(agla_adj_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, fixed_mask, goff), B(),
+                                       static_cast<double*>(dots_dev), stream);
   }
 
-  // ... followed by the adjoint of the projection y = P(c_{n-1}): gc becomes the cotangent of c_{n-1}
+  // ... followed by the adjoint of the projection y = P(c_{n-1}) against mag_fm (under a constraint where(M, 0, m)): gc becomes the
+  // cotangent of c_{n-1}
   int agla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], void* a, void* gc, void* gd,
-                        void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) override {
+                        void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm, const void* fixed_mask, void* goff) override {
     SI_CHECK(mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
-    SI_TRY(agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots_dev));
+    SI_TRY(agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots_dev, fixed_mask, goff));
     return proj_adjoint_stages(static_cast<T*>(gc), static_cast<const T*>(c_prev), static_cast<const T*>(mag_fm),
                                static_cast<T*>(gmag_fm));
   }
 
-  // The closing step t_1 = c_1 = d_1 = P(c_0): gc <- (a + gc + gd) / env, then the projection's adjoint at c_0
-  int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm) override {
-    SI_CHECK(c0 && a && gc && mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
-    AglaAdjArgs<T> p{};
-    p.a = const_cast<T*>(static_cast<const T*>(a));
-    p.gc = static_cast<T*>(gc);
-    p.gd = const_cast<T*>(static_cast<const T*>(gd));
-    p.env = env.as<T>();
-    p.L = length;
-    p.first = 1;
-    SI_TRY(agla_step_adjoint_launch<T>(p, B(), nullptr, stream));
-    return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
-  }
-
-  // The adjoint of constrained AGLA's extrapolation step n >= 2 (kernels_cgla_adjoint.h): agla_extrap_adjoint with the sample mask
-  // (nullptr: no known sample) and goff, which it accumulates.  Only agla_adj_part is written beside the caller's arrays.
-  int cgla_extrap_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask, void* a,
-                          void* gc, void* gd, void* goff, void* c_prev, void* dots_dev) override {
-    SI_CHECK(t_n && t_nm1 && coef && a && gc && goff && c_prev && dots_dev, SPECINV_EINVAL, "null pointer");
-    SI_CHECK(coef[0] >= 0 && coef[1] >= 0 && coef[3] >= 0 && coef[4] >= 0 && coef[2] > 0, SPECINV_EINVAL,
-             "alpha and beta must be >= 0, gamma > 0");
-    SI_CHECK(gd != nullptr || coef[2] == 1.0, SPECINV_EINVAL, "gamma = %g needs gd", coef[2]);
-    SI_TRY(agla_adj_part.reserve((size_t)3 * kAglaAdjMaxGrid * sizeof(double)));
-    CglaAdjArgs<T> p{};
-    p.a = static_cast<T*>(a);
-    p.gc = static_cast<T*>(gc);
-    p.gd = static_cast<T*>(gd);
-    p.goff = static_cast<T*>(goff);
-    p.tn = static_cast<const T*>(t_n);
-    p.tp = static_cast<const T*>(t_nm1);
-    p.tpp = static_cast<const T*>(t_nm2);
-    p.env = env.as<T>();
-    p.mask = static_cast<const uint8_t*>(fixed_mask);
-    p.c_prev = static_cast<T*>(c_prev);
-    p.partials = agla_adj_part.as<double>();
-    p.alpha = (T)coef[0];
-    p.beta = (T)coef[1];
-    p.gamma = (T)coef[2];
-    p.one_minus_gamma = (T)(1.0 - coef[2]);
-    p.alpha_p = (T)coef[3];
-    p.beta_p = (T)coef[4];
-    p.L = length;
-    return cgla_step_adjoint_launch<T>(p, B(), static_cast<double*>(dots_dev), stream);
-  }
-
-  // ... followed by the adjoint of the projection y = P(c_{n-1}) against mag_fm = where(M, 0, m): gc becomes the cotangent of c_{n-1}
-  int cgla_step_adjoint(const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5], const void* fixed_mask, void* a,
-                        void* gc, void* gd, void* goff, void* c_prev, void* dots_dev, const void* mag_fm, void* gmag_fm) override {
-    SI_CHECK(mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
-    SI_TRY(cgla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots_dev));
-    return proj_adjoint_stages(static_cast<T*>(gc), static_cast<const T*>(c_prev), static_cast<const T*>(mag_fm),
+  // The closing step t_1 = c_1 = d_1 = P(c_0): gc <- (a + gc + gd) / env, then the projection's adjoint at c_0.  Under a constraint
+  // t_1 = where(W, off, P(c_0) + off): s = a + gc + gd, goff += s, gc <- (W ? 0 : s) / env.
+  int agla_first_adjoint(const void* c0, const void* a, void* gc, const void* gd, const void* mag_fm, void* gmag_fm,
+                         const void* fixed_mask, void* goff) override {
+    SI_CHECK(c0 && a && gc && mag_fm && gmag_fm && (goff || !fixed_mask), SPECINV_EINVAL, "null pointer");
+    SI_TRY(agla_step_adjoint_launch<T>(agla_adj_args(nullptr, nullptr, nullptr, nullptr, a, gc, gd, nullptr, fixed_mask, goff), B(),
+                                       nullptr, stream));
+    return proj_adjoint_stages(static_cast<T*>(gc), static_cast<const T*>(c0), static_cast<const T*>(mag_fm),
                                static_cast<T*>(gmag_fm));
-  }
-
-  // The closing step t_1 = c_1 = d_1 = where(W, off, P(c_0) + off): s = a + gc + gd, goff += s, gc <- (W ? 0 : s) / env, then the
-  // projection's adjoint at c_0
-  int cgla_first_adjoint(const void* c0, const void* fixed_mask, const void* a, void* gc, const void* gd, void* goff, const void* mag_fm,
-                         void* gmag_fm) override {
-    SI_CHECK(c0 && a && gc && goff && mag_fm && gmag_fm, SPECINV_EINVAL, "null pointer");
-    CglaAdjArgs<T> p{};
-    p.a = const_cast<T*>(static_cast<const T*>(a));
-    p.gc = static_cast<T*>(gc);
-    p.gd = const_cast<T*>(static_cast<const T*>(gd));
-    p.goff = static_cast<T*>(goff);
-    p.env = env.as<T>();
-    p.mask = static_cast<const uint8_t*>(fixed_mask);
-    p.L = length;
-    p.first = 1;
-    SI_TRY(cgla_step_adjoint_launch<T>(p, B(), nullptr, stream));
-    return proj_adjoint_stages(p.gc, static_cast<const T*>(c0), static_cast<const T*>(mag_fm), static_cast<T*>(gmag_fm));
   }
 
   // gla_projection's forward pass: the transform, the projection in the internal layout, the inverse transform.  Only scratch is

@@ -538,7 +538,8 @@ int specinv_agla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void*
                                 void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out) {
   AGLA_ADJ_ARGS("specinv_agla_extrap_adjoint");
   ENTER(plan);
-  return plan->impl->agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out);
+  return plan->impl->agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out, nullptr,
+                                         nullptr);
 }
 int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
                               void* a_inout, void* gc_inout, void* gd_inout, void* c_prev_out, void* dots_dev_out,
@@ -547,14 +548,14 @@ int specinv_agla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t
   SI_CHECK(mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_agla_step_adjoint: NULL %s", mag_fm ? "gmag_fm_accum" : "mag_fm");
   ENTER(plan);
   return plan->impl->agla_step_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out, mag_fm,
-                                       gmag_fm_accum);
+                                       gmag_fm_accum, nullptr, nullptr);
 }
 int specinv_agla_first_adjoint(specinv_plan* plan, const void* c0, const void* a, void* gc_inout, const void* gd, const void* mag_fm,
                                void* gmag_fm_accum) {
   SI_CHECK(c0 && a && gc_inout && mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_agla_first_adjoint: NULL %s",
            !c0 ? "c0" : !a ? "a" : !gc_inout ? "gc_inout" : !mag_fm ? "mag_fm" : "gmag_fm_accum");
   ENTER(plan);
-  return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum);
+  return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum, nullptr, nullptr);
 }
 #define CGLA_ADJ_ARGS(name)                                                                     \
   AGLA_ADJ_ARGS(name);                                                                          \
@@ -565,8 +566,8 @@ int specinv_cgla_extrap_adjoint(specinv_plan* plan, const void* t_n, const void*
                                 void* c_prev_out, void* dots_dev_out) {
   CGLA_ADJ_ARGS("specinv_cgla_extrap_adjoint");
   ENTER(plan);
-  return plan->impl->cgla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a_inout, gc_inout, gd_inout, goff_accum, c_prev_out,
-                                         dots_dev_out);
+  return plan->impl->agla_extrap_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out, fixed_mask,
+                                         goff_accum);
 }
 int specinv_cgla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t_nm1, const void* t_nm2, const double coef[5],
                               const void* fixed_mask, void* a_inout, void* gc_inout, void* gd_inout, void* goff_accum,
@@ -574,15 +575,15 @@ int specinv_cgla_step_adjoint(specinv_plan* plan, const void* t_n, const void* t
   CGLA_ADJ_ARGS("specinv_cgla_step_adjoint");
   SI_CHECK(mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_cgla_step_adjoint: NULL %s", mag_fm ? "gmag_fm_accum" : "mag_fm");
   ENTER(plan);
-  return plan->impl->cgla_step_adjoint(t_n, t_nm1, t_nm2, coef, fixed_mask, a_inout, gc_inout, gd_inout, goff_accum, c_prev_out,
-                                       dots_dev_out, mag_fm, gmag_fm_accum);
+  return plan->impl->agla_step_adjoint(t_n, t_nm1, t_nm2, coef, a_inout, gc_inout, gd_inout, c_prev_out, dots_dev_out, mag_fm,
+                                       gmag_fm_accum, fixed_mask, goff_accum);
 }
 int specinv_cgla_first_adjoint(specinv_plan* plan, const void* c0, const void* fixed_mask, const void* a, void* gc_inout, const void* gd,
                                void* goff_accum, const void* mag_fm, void* gmag_fm_accum) {
   SI_CHECK(c0 && a && gc_inout && goff_accum && mag_fm && gmag_fm_accum, SPECINV_EINVAL, "specinv_cgla_first_adjoint: NULL %s",
            !c0 ? "c0" : !a ? "a" : !gc_inout ? "gc_inout" : !goff_accum ? "goff_accum" : !mag_fm ? "mag_fm" : "gmag_fm_accum");
   ENTER(plan);
-  return plan->impl->cgla_first_adjoint(c0, fixed_mask, a, gc_inout, gd, goff_accum, mag_fm, gmag_fm_accum);
+  return plan->impl->agla_first_adjoint(c0, a, gc_inout, gd, mag_fm, gmag_fm_accum, fixed_mask, goff_accum);
 }
 int specinv_project(specinv_plan* plan, const void* x, const void* mag_fm, void* y_out) {
   SI_CHECK(x && mag_fm && y_out, SPECINV_EINVAL, "specinv_project: NULL %s", !x ? "x" : !mag_fm ? "mag_fm" : "y_out");

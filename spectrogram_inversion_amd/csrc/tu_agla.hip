@@ -15,8 +15,13 @@ int launch_v(const AglaStepArgs<T>& a0, int batch, hipStream_t stream) {
   if (a.n_units == 0) return SPECINV_OK;
   // memory-bound: eight workgroups of four waves per CU cover the chip, the rest is walked
   const dim3 grid((unsigned)std::min<int64_t>(ceil_div(a.n_units, 256), 256 * 8)), blk(256);
-  if (a.d != nullptr) hipLaunchKernelGGL((k_agla_step<T, V, true>), grid, blk, 0, stream, a);
-  else hipLaunchKernelGGL((k_agla_step<T, V, false>), grid, blk, 0, stream, a);
+  if (a.offset != nullptr) {
+    if (a.d != nullptr) hipLaunchKernelGGL((k_agla_step<T, V, true, true>), grid, blk, 0, stream, a);
+    else hipLaunchKernelGGL((k_agla_step<T, V, false, true>), grid, blk, 0, stream, a);
+  } else {
+    if (a.d != nullptr) hipLaunchKernelGGL((k_agla_step<T, V, true, false>), grid, blk, 0, stream, a);
+    else hipLaunchKernelGGL((k_agla_step<T, V, false, false>), grid, blk, 0, stream, a);
+  }
   SI_HIP(hipGetLastError());
   return SPECINV_OK;
 }
@@ -25,19 +30,15 @@ int launch_v(const AglaStepArgs<T>& a0, int batch, hipStream_t stream) {
 
 template <typename T>
 int agla_step_launch(AglaStepArgs<T> a, int batch, hipStream_t stream) {
-  SI_CHECK(a.x != nullptr && a.t != nullptr && a.L >= 1 && batch >= 1, SPECINV_EINVAL, "agla step: bad arguments");
+  SI_CHECK(a.x != nullptr && a.t != nullptr && (a.offset != nullptr || a.mask == nullptr) && a.L >= 1 && batch >= 1, SPECINV_EINVAL,
+           "agla step: bad arguments");
   SI_CHECK(a.tail == nullptr || (a.hop >= 1 && a.nb >= 1 && a.nchunks >= 2 && a.n_frames >= 1), SPECINV_EINVAL,
            "agla step: bad tail geometry");
-  // samples per thread: every row (x, t, d, the tails) starts at a multiple of L (hop) elements from an aligned base
-  auto aligned = [](const void* p, int v) { return reinterpret_cast<uintptr_t>(p) % (v * sizeof(T)) == 0; };
-  auto divides = [&](int v) {
-    return a.L % v == 0 && (a.tail == nullptr || a.hop % v == 0) && aligned(a.x, v) && aligned(a.t, v) && aligned(a.d, v) &&
-           aligned(a.tail, v);
-  };
+  const int v = misi_vec_width<T>(a.L, a.tail != nullptr ? a.hop : 0, {a.x, a.t, a.d, a.offset, a.tail}, a.mask);
   if constexpr (sizeof(T) == 4) {
-    if (divides(4)) return launch_v<T, 4>(a, batch, stream);
+    if (v == 4) return launch_v<T, 4>(a, batch, stream);
   }
-  if (divides(2)) return launch_v<T, 2>(a, batch, stream);
+  if (v == 2) return launch_v<T, 2>(a, batch, stream);
   return launch_v<T, 1>(a, batch, stream);
 }
 

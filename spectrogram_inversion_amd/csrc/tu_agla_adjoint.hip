@@ -39,38 +39,33 @@ int launch_v(const AglaAdjArgs<T>& p0, int batch, double* dots_dev, hipStream_t 
   // memory-bound: eight workgroups of four waves per CU cover the chip, the rest is walked
   const int n_wg = (int)std::min<int64_t>(ceil_div(p.n_units, 256), kAglaAdjMaxGrid);
   const dim3 grid((unsigned)n_wg), blk(256);
-  if (p.gd != nullptr) hipLaunchKernelGGL((k_agla_step_adjoint<T, V, true>), grid, blk, 0, stream, p);
-  else hipLaunchKernelGGL((k_agla_step_adjoint<T, V, false>), grid, blk, 0, stream, p);
+  if (p.goff != nullptr) {
+    if (p.gd != nullptr) hipLaunchKernelGGL((k_agla_step_adjoint<T, V, true, true>), grid, blk, 0, stream, p);
+    else hipLaunchKernelGGL((k_agla_step_adjoint<T, V, false, true>), grid, blk, 0, stream, p);
+  } else {
+    if (p.gd != nullptr) hipLaunchKernelGGL((k_agla_step_adjoint<T, V, true, false>), grid, blk, 0, stream, p);
+    else hipLaunchKernelGGL((k_agla_step_adjoint<T, V, false, false>), grid, blk, 0, stream, p);
+  }
   SI_HIP(hipGetLastError());
   if (p.first) return SPECINV_OK;
-  return agla_dots_finish_launch(p.partials, n_wg, (double)p.gamma, dots_dev, stream);
-}
-
-}  // namespace
-
-int agla_dots_finish_launch(const double* partials, int n_part, double gamma, double* dots_dev, hipStream_t stream) {
-  hipLaunchKernelGGL(k_agla_dots_finish, dim3(1), dim3(256), 0, stream, partials, n_part, gamma, dots_dev);
+  hipLaunchKernelGGL(k_agla_dots_finish, dim3(1), dim3(256), 0, stream, p.partials, n_wg, (double)p.gamma, dots_dev);
   SI_HIP(hipGetLastError());
   return SPECINV_OK;
 }
 
+}  // namespace
+
 template <typename T>
 int agla_step_adjoint_launch(AglaAdjArgs<T> p, int batch, double* dots_dev, hipStream_t stream) {
-  SI_CHECK(p.a != nullptr && p.gc != nullptr && p.env != nullptr && p.L >= 1 && batch >= 1, SPECINV_EINVAL,
-           "agla step adjoint: bad arguments");
+  SI_CHECK(p.a != nullptr && p.gc != nullptr && (p.goff != nullptr || p.mask == nullptr) && p.env != nullptr && p.L >= 1 && batch >= 1,
+           SPECINV_EINVAL, "agla step adjoint: bad arguments");
   SI_CHECK(p.first || (p.tn != nullptr && p.tp != nullptr && p.c_prev != nullptr && p.partials != nullptr && dots_dev != nullptr),
            SPECINV_EINVAL, "agla step adjoint: bad arguments");
-  // samples per thread: every row (the cotangents, the t's, c_prev, the envelope) starts at a multiple of L elements from an
-  // aligned base
-  auto aligned = [](const void* q, int v) { return reinterpret_cast<uintptr_t>(q) % (v * sizeof(T)) == 0; };
-  auto divides = [&](int v) {
-    return p.L % v == 0 && aligned(p.a, v) && aligned(p.gc, v) && aligned(p.gd, v) && aligned(p.tn, v) && aligned(p.tp, v) &&
-           aligned(p.tpp, v) && aligned(p.env, v) && aligned(p.c_prev, v);
-  };
+  const int v = misi_vec_width<T>(p.L, 0, {p.a, p.gc, p.gd, p.goff, p.tn, p.tp, p.tpp, p.env, p.c_prev}, p.mask);
   if constexpr (sizeof(T) == 4) {
-    if (divides(4)) return launch_v<T, 4>(p, batch, dots_dev, stream);
+    if (v == 4) return launch_v<T, 4>(p, batch, dots_dev, stream);
   }
-  if (divides(2)) return launch_v<T, 2>(p, batch, dots_dev, stream);
+  if (v == 2) return launch_v<T, 2>(p, batch, dots_dev, stream);
   return launch_v<T, 1>(p, batch, dots_dev, stream);
 }
 

@@ -32,16 +32,11 @@ int misi_mix_launch(MisiMixArgs<T> a, int n_mix, hipStream_t stream) {
   SI_CHECK(a.x != nullptr && a.mix != nullptr && a.K >= 1 && a.L >= 1 && n_mix >= 1, SPECINV_EINVAL, "misi mix: bad arguments");
   SI_CHECK(a.tail == nullptr || (a.hop >= 1 && a.nb >= 1 && a.nchunks >= 2 && a.n_frames >= 1), SPECINV_EINVAL,
            "misi mix: bad tail geometry");
-  // samples per thread: every row (x, the mixture, the tails) starts at a multiple of L (hop) elements from an aligned base
-  auto divides = [&](int v) {
-    return a.L % v == 0 && (a.tail == nullptr || a.hop % v == 0) && reinterpret_cast<uintptr_t>(a.x) % (v * sizeof(T)) == 0 &&
-           reinterpret_cast<uintptr_t>(a.mix) % (v * sizeof(T)) == 0 &&
-           (a.tail == nullptr || reinterpret_cast<uintptr_t>(a.tail) % (v * sizeof(T)) == 0);
-  };
+  const int v = misi_vec_width<T>(a.L, a.tail != nullptr ? a.hop : 0, {a.x, a.mix, a.tail});
   if constexpr (sizeof(T) == 4) {
-    if (divides(4)) return launch_v<T, 4>(a, n_mix, stream);
+    if (v == 4) return launch_v<T, 4>(a, n_mix, stream);
   }
-  if (divides(2)) return launch_v<T, 2>(a, n_mix, stream);
+  if (v == 2) return launch_v<T, 2>(a, n_mix, stream);
   return launch_v<T, 1>(a, n_mix, stream);
 }
 

@@ -29,13 +29,11 @@ int launch_v(const MisiMixAdjArgs<T>& a0, int n_mix, hipStream_t stream) {
 
 template <typename T, bool DIV_ENV>
 int launch_env(const MisiMixAdjArgs<T>& a, int n_mix, hipStream_t stream) {
-  // samples per thread: every row (g, gmix, the envelope) starts at a multiple of L elements from an aligned base
-  auto aligned = [](const void* p, int v) { return reinterpret_cast<uintptr_t>(p) % (v * sizeof(T)) == 0; };
-  auto divides = [&](int v) { return a.L % v == 0 && aligned(a.g, v) && aligned(a.gmix, v) && aligned(a.env, v); };
+  const int v = misi_vec_width<T>(a.L, 0, {a.g, a.gmix, a.env});
   if constexpr (sizeof(T) == 4) {
-    if (divides(4)) return launch_v<T, 4, DIV_ENV>(a, n_mix, stream);
+    if (v == 4) return launch_v<T, 4, DIV_ENV>(a, n_mix, stream);
   }
-  if (divides(2)) return launch_v<T, 2, DIV_ENV>(a, n_mix, stream);
+  if (v == 2) return launch_v<T, 2, DIV_ENV>(a, n_mix, stream);
   return launch_v<T, 1, DIV_ENV>(a, n_mix, stream);
 }
 

@@ -290,12 +290,16 @@ class Plan:
                                               mix.shape[1], n_src))
         self._method = "misi"
 
-    def misi_iterate(self, n_iter: int, eval_last: bool = False):
-        """`n_iter` MISI iterations (projection launch + coupling launch each); the evaluation sums of the last if asked."""
+    def _iterate(self, fn, n_iter, eval_last):
+        """`fn` (one of `specinv_*_iterate`) for `n_iter` iterations; the four evaluation sums of the last if asked."""
         self._sync_stream()
         sums = (C.c_double * 4)()
-        _lib.check(self.lib.specinv_misi_iterate(self._h, int(n_iter), int(eval_last), sums))
+        _lib.check(fn(self._h, int(n_iter), int(eval_last), sums))
         return list(sums) if eval_last else None
+
+    def misi_iterate(self, n_iter: int, eval_last: bool = False):
+        """`n_iter` MISI iterations (projection launch + coupling launch each); the evaluation sums of the last if asked."""
+        return self._iterate(self.lib.specinv_misi_iterate, n_iter, eval_last)
 
     def agla_init(self, init_spec, mag, alpha, beta, gamma):
         """Accelerated Griffin-Lim (include/specinv.h: specinv_agla_init): `init_spec` (batch, F, T) complex is the start (None:
@@ -330,29 +334,19 @@ class Plan:
             _lib.check(self.lib.specinv_agla_constrain(self._h, None, None))
             return
         off = self._in(offset, self.dtype, (self.batch, self.length))
-        w = None
-        if fixed_mask is not None:
-            assert fixed_mask.dtype in (torch.bool, torch.uint8), f"fixed_mask must be bool or uint8, got {fixed_mask.dtype}"
-            w = self._in(fixed_mask.to(torch.uint8), torch.uint8, (self.batch, self.length))
+        w = self._fixed_mask(fixed_mask)
         _lib.check(self.lib.specinv_agla_constrain(self._h, off.data_ptr(), None if w is None else w.data_ptr()))
 
     def agla_iterate(self, n_iter: int, eval_last: bool = False):
         """`n_iter` AGLA iterations (projection launch + extrapolation launch each); the evaluation sums of the last if asked."""
-        self._sync_stream()
-        sums = (C.c_double * 4)()
-        _lib.check(self.lib.specinv_agla_iterate(self._h, int(n_iter), int(eval_last), sums))
-        return list(sums) if eval_last else None
+        return self._iterate(self.lib.specinv_agla_iterate, n_iter, eval_last)
 
     def iterate(self, n_iter: int, eval_last: bool = False):
         if self._method == "misi":
             return self.misi_iterate(n_iter, eval_last)
         if self._method == "agla":
             return self.agla_iterate(n_iter, eval_last)
-        self._sync_stream()
-        fn = self.lib.specinv_gla_iterate if self._method == "gla" else self.lib.specinv_admm_iterate
-        sums = (C.c_double * 4)()
-        _lib.check(fn(self._h, int(n_iter), int(eval_last), sums))
-        return list(sums) if eval_last else None
+        return self._iterate(self.lib.specinv_gla_iterate if self._method == "gla" else self.lib.specinv_admm_iterate, n_iter, eval_last)
 
     def iterate_dev(self, n_iter: int, out: torch.Tensor):
         """`iterate(n_iter, eval_last=True)` with the evaluation's four sums left in `out` (4 float64 on the plan's device): no
@@ -482,89 +476,75 @@ class Plan:
         _lib.check(self.lib.specinv_misi_step_adjoint(self._h, n_src, x_prev.data_ptr(), mag_fm.data_ptr(), gp, mp,
                                                       self._inout(gmag_fm, fm, "gmag_fm")))
 
-    def _agla_adjoint_args(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots):
-        sig = (self.batch, self.length)
-        t_n, t_nm1 = self._in(t_n, self.dtype, sig), self._in(t_nm1, self.dtype, sig)
-        t_nm2 = None if t_nm2 is None else self._in(t_nm2, self.dtype, sig)
-        assert len(coef) == 5, "coef is (alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1})"
-        assert dots.dtype == torch.float64 and dots.numel() == 3 and dots.is_contiguous() and dots.device == self.device, \
-            f"dots must be 3 contiguous float64 on {self.device}"
-        keep = (t_n, t_nm1, t_nm2)                                 # (converted copies stay alive until the call is enqueued)
-        return keep, (t_n.data_ptr(), t_nm1.data_ptr(), None if t_nm2 is None else t_nm2.data_ptr(),
-                      (C.c_double * 5)(*[float(v) for v in coef]), self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
-                      None if gd is None else self._inout(gd, sig, "gd"), self._inout(c_prev, sig, "c_prev"),
-                      C.c_void_p(dots.data_ptr()))
+    def _fixed_mask(self, fixed_mask):
+        """A mask of known samples as (batch, length) uint8 on the device; None stays None."""
+        if fixed_mask is None:
+            return None
+        assert fixed_mask.dtype in (torch.bool, torch.uint8), f"fixed_mask must be bool or uint8, got {fixed_mask.dtype}"
+        return self._in(fixed_mask.to(torch.uint8), torch.uint8, (self.batch, self.length))
+
+    def _agla_adjoint(self, kind, lead, a, gc, gd, out=None, proj=None, constraint=None):
+        """One call of `specinv_agla_<kind>_adjoint` or, with `constraint` = (fixed_mask, goff), `specinv_cgla_<kind>_adjoint`.
+        `lead`: (t_n, t_nm1, t_nm2, coef) of a step n >= 2, (c0,) of the closing one; `out`: (c_prev, dots) of a step; `proj`:
+        (mag_fm, gmag_fm) where the projection's adjoint follows.  The C argument order is lead, [mask], a, gc, gd, [goff], out,
+        proj."""
+        self._sync_stream()
+        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
+        ptr = lambda t: None if t is None else t.data_ptr()                                   # noqa: E731
+        keep = [None if t is None else self._in(t, self.dtype, sig) for t in lead[:3]]         # (converted copies stay alive)
+        args = [ptr(t) for t in keep]
+        if len(lead) == 4:
+            assert len(lead[3]) == 5, "coef is (alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1})"
+            args.append((C.c_double * 5)(*[float(v) for v in lead[3]]))
+        mag_fm = None if proj is None else self._in(proj[0], self.dtype, fm)
+        if constraint is not None:
+            w = self._fixed_mask(constraint[0])
+            args.append(ptr(w))
+        args += [self._inout(a, sig, "a"), self._inout(gc, sig, "gc"), None if gd is None else self._inout(gd, sig, "gd")]
+        if constraint is not None:
+            args.append(self._inout(constraint[1], sig, "goff"))
+        if out is not None:
+            c_prev, dots = out
+            assert dots.dtype == torch.float64 and dots.numel() == 3 and dots.is_contiguous() and dots.device == self.device, \
+                f"dots must be 3 contiguous float64 on {self.device}"
+            args += [self._inout(c_prev, sig, "c_prev"), C.c_void_p(dots.data_ptr())]
+        if proj is not None:
+            args += [mag_fm.data_ptr(), self._inout(proj[1], fm, "gmag_fm")]
+        fn = getattr(self.lib, f"specinv_{'agla' if constraint is None else 'cgla'}_{kind}_adjoint")
+        _lib.check(fn(self._h, *args))
 
     def agla_extrap_adjoint(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots):
         """Adjoint of AGLA's extrapolation step n >= 2 (`specinv_agla_extrap_adjoint`), in place on the sweep's state `a`, `gc`,
         `gd` (None: every gamma is 1), all (batch, length): `coef` = (alpha_n, beta_n, gamma_n, alpha_{n-1}, beta_{n-1}),
         `t_nm2` None for n = 2; `c_prev` receives c_{n-1}, `dots` (3 float64 on the device) the gradients of alpha_n, beta_n,
         gamma_n."""
-        self._sync_stream()
-        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
-        _lib.check(self.lib.specinv_agla_extrap_adjoint(self._h, *ptrs))
+        self._agla_adjoint("extrap", (t_n, t_nm1, t_nm2, coef), a, gc, gd, (c_prev, dots))
 
     def agla_step_adjoint(self, t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots, mag_fm, gmag_fm):
         """`agla_extrap_adjoint`, then the adjoint of the projection at `c_prev` (`specinv_agla_step_adjoint`): `gc` becomes the
         cotangent of c_{n-1}, `gmag_fm` gains the magnitude's.  `mag_fm` and `gmag_fm` are frame-major, (batch, n_frames, n_freq)."""
-        self._sync_stream()
-        fm = (self.batch, self.n_frames, self.n_freq)
-        mag_fm = self._in(mag_fm, self.dtype, fm)
-        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
-        _lib.check(self.lib.specinv_agla_step_adjoint(self._h, *ptrs, mag_fm.data_ptr(), self._inout(gmag_fm, fm, "gmag_fm")))
+        self._agla_adjoint("step", (t_n, t_nm1, t_nm2, coef), a, gc, gd, (c_prev, dots), (mag_fm, gmag_fm))
 
     def agla_first_adjoint(self, c0, a, gc, gd, mag_fm, gmag_fm):
         """The closing step of AGLA's sweep (`specinv_agla_first_adjoint`): `gc` becomes the cotangent of `c0` = ISTFT(start) from
         `a`, `gc` and `gd` (None: absent), the cotangents of t_1, c_1 and d_1; `gmag_fm` gains the magnitude's."""
-        self._sync_stream()
-        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
-        c0, mag_fm = self._in(c0, self.dtype, sig), self._in(mag_fm, self.dtype, fm)
-        _lib.check(self.lib.specinv_agla_first_adjoint(self._h, c0.data_ptr(), self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
-                                                       None if gd is None else self._inout(gd, sig, "gd"), mag_fm.data_ptr(),
-                                                       self._inout(gmag_fm, fm, "gmag_fm")))
-
-    def _fixed_mask(self, fixed_mask):
-        """The sample mask of the constrained sweep as (batch, length) uint8 on the device; None stays None."""
-        if fixed_mask is None:
-            return None
-        assert fixed_mask.dtype in (torch.bool, torch.uint8), f"fixed_mask must be bool or uint8, got {fixed_mask.dtype}"
-        return self._in(fixed_mask.to(torch.uint8), torch.uint8, (self.batch, self.length))
+        self._agla_adjoint("first", (c0,), a, gc, gd, None, (mag_fm, gmag_fm))
 
     def cgla_extrap_adjoint(self, t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots):
         """`agla_extrap_adjoint` under the constraint of `agla_constrain` (`specinv_cgla_extrap_adjoint`): `fixed_mask`
         (batch, length) bool / uint8 or None is the mask of known samples, `goff` (batch, length) gains the cotangent of the
         constraint's offset."""
-        self._sync_stream()
-        w = self._fixed_mask(fixed_mask)
-        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
-        goff = self._inout(goff, (self.batch, self.length), "goff")
-        _lib.check(self.lib.specinv_cgla_extrap_adjoint(self._h, *ptrs[:4], None if w is None else w.data_ptr(), *ptrs[4:7], goff,
-                                                        *ptrs[7:]))
+        self._agla_adjoint("extrap", (t_n, t_nm1, t_nm2, coef), a, gc, gd, (c_prev, dots), None, (fixed_mask, goff))
 
     def cgla_step_adjoint(self, t_n, t_nm1, t_nm2, coef, fixed_mask, a, gc, gd, goff, c_prev, dots, mag_fm, gmag_fm):
         """`cgla_extrap_adjoint`, then the adjoint of the projection at `c_prev` (`specinv_cgla_step_adjoint`); `mag_fm` is the
         target with zeros under the mask of known bins, frame-major."""
-        self._sync_stream()
-        fm = (self.batch, self.n_frames, self.n_freq)
-        mag_fm = self._in(mag_fm, self.dtype, fm)
-        w = self._fixed_mask(fixed_mask)
-        keep, ptrs = self._agla_adjoint_args(t_n, t_nm1, t_nm2, coef, a, gc, gd, c_prev, dots)
-        goff = self._inout(goff, (self.batch, self.length), "goff")
-        _lib.check(self.lib.specinv_cgla_step_adjoint(self._h, *ptrs[:4], None if w is None else w.data_ptr(), *ptrs[4:7], goff,
-                                                      *ptrs[7:], mag_fm.data_ptr(), self._inout(gmag_fm, fm, "gmag_fm")))
+        self._agla_adjoint("step", (t_n, t_nm1, t_nm2, coef), a, gc, gd, (c_prev, dots), (mag_fm, gmag_fm), (fixed_mask, goff))
 
     def cgla_first_adjoint(self, c0, fixed_mask, a, gc, gd, goff, mag_fm, gmag_fm):
         """The closing step of the constrained sweep (`specinv_cgla_first_adjoint`): `agla_first_adjoint` with the select of the
         known samples; `goff` gains the cotangent of the constraint's offset."""
-        self._sync_stream()
-        sig, fm = (self.batch, self.length), (self.batch, self.n_frames, self.n_freq)
-        c0, mag_fm = self._in(c0, self.dtype, sig), self._in(mag_fm, self.dtype, fm)
-        w = self._fixed_mask(fixed_mask)
-        _lib.check(self.lib.specinv_cgla_first_adjoint(self._h, c0.data_ptr(), None if w is None else w.data_ptr(),
-                                                       self._inout(a, sig, "a"), self._inout(gc, sig, "gc"),
-                                                       None if gd is None else self._inout(gd, sig, "gd"),
-                                                       self._inout(goff, sig, "goff"), mag_fm.data_ptr(),
-                                                       self._inout(gmag_fm, fm, "gmag_fm")))
+        self._agla_adjoint("first", (c0,), a, gc, gd, None, (mag_fm, gmag_fm), (fixed_mask, goff))
 
     @property
     def project_adjoint_kind(self) -> str:

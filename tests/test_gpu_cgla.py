@@ -1,4 +1,4 @@
-"""constrained_griffin_lim on the device (`specinv_agla_constrain`, csrc/kernels_cgla.h) through `Plan` and the public function,
+"""constrained_griffin_lim on the device (`specinv_agla_constrain`, csrc/kernels_agla.h) through `Plan` and the public function,
 against its NumPy restatement (tests/_cgla_oracle.py): every kernel family the projection can take - the step kernel edits the
 state each of them reads next - both arms of the kernel, its 16- / 8- / 4-byte accesses, mask edges inside a thread's vector and
 masks that differ from item to item.  Needs an MI355X: `-m gpu`."""

@@ -1,7 +1,7 @@
 """`constrained_unfolded` on the device: its forward against `constrained_griffin_lim` and `agla_unfolded` (bits) and the torch
 restatement of the constrained oracle (tests/_cgla_torch.py), its gradients against autograd on that restatement, against central
 differences of the inference path and against the same iteration composed from `gla_projection`, `stft`, `istft` and torch ops,
-`specinv_cgla_extrap_adjoint` (csrc/kernels_cgla_adjoint.h) alone against NumPy, and the layer's properties.  Needs an MI355X:
+`specinv_cgla_extrap_adjoint` (csrc/kernels_agla_adjoint.h) alone against NumPy, and the layer's properties.  Needs an MI355X:
 `-m gpu`."""
 import ctypes as C
 

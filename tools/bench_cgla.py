@@ -6,9 +6,9 @@ the unconstrained AGLA iteration in the same process: one JSON line, also writte
     python tools/bench_cgla.py --step-only [--gamma G]      (constrained iterations alone: the process a kernel trace wraps)
 
 <tag>.free_ms_per_iter    one unconstrained iteration (projection launch + k_agla_step), gamma = 1 (fgla) and gamma = 0.7 (general)
-<tag>.spec_ms_per_iter    ... with the low quarter band known (projection launch + k_cgla_step, no sample mask)
+<tag>.spec_ms_per_iter    ... with the low quarter band known (projection launch + k_agla_step, no sample mask)
 <tag>.both_ms_per_iter    ... and two thirds of the samples known (the mask read too); over_free: its ratio to the first
-<tag>.kernel_trace        k_cgla_step with both constraints - unless --no-trace - in a rocprofv3 kernel trace of a child process: its
+<tag>.kernel_trace        k_agla_step with both constraints - unless --no-trace - in a rocprofv3 kernel trace of a child process: its
                           median, bytes = 5 (gamma = 1) or 7 transfers of 4 bytes per sample plus the mask byte and the read of the
                           chunk tails, and their rate against the 8 TB/s peak
 """
@@ -54,7 +54,7 @@ def begin(plan, start, con, mode, gamma):
 
 
 def step_bytes(plan, gamma):
-    """What k_cgla_step must move with both constraints: x and t read and written, offset read (d read and written too with
+    """What k_agla_step must move with both constraints: x and t read and written, offset read (d read and written too with
     gamma != 1), a mask byte, the chunk tails read"""
     geo = plan.launch_geometry
     tails = B * (geo["chunks"] - 1) * (N_FFT // HOP - 1) * HOP if geo["kernel"].startswith("k_fused") and geo["chunks"] > 1 else 0
@@ -62,7 +62,7 @@ def step_bytes(plan, gamma):
 
 
 def trace_step(gamma, iters):
-    """Median duration of k_cgla_step in a kernel trace of a child process running constrained iterations alone (None: no
+    """Median duration of k_agla_step in a kernel trace of a child process running constrained iterations alone (None: no
     profiler).  The child runs under `timeout -k 10`; any exit status but 0 raises TraceFailed and the caller stops there."""
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
@@ -81,12 +81,12 @@ def trace_step(gamma, iters):
         with open(files[-1], newline="") as fh:
             for row in csv.DictReader(fh):
                 name = row["Kernel_Name"]
-                if "k_cgla_step" in name or "k_fused4" in name:
+                if "k_agla_step" in name or "k_fused4" in name:
                     per.setdefault(name.split("(")[0].replace("void specinv::", "").replace("fast::", ""), []).append(
                         (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
         res = {}
         for name, d in per.items():
-            if "k_cgla_step" in name:
+            if "k_agla_step" in name:
                 d = d[1:]        # the first launch after the one agla_init of --step-only has no history: no t or d to read
             res[name] = {"calls": len(d), "median_us": round(statistics.median(d), 2), "min_us": round(min(d), 2),
                          "max_us": round(max(d), 2)}
@@ -140,7 +140,7 @@ def main():
                 tr, failed = {"error": str(e)}, str(e)
             entry["kernel_trace"] = tr
             for name, st in (tr or {}).items():
-                if "k_cgla_step" in name and "median_us" in st:
+                if "k_agla_step" in name and "median_us" in st:
                     st["TBps"] = round(nbytes[gamma] / (st["median_us"] * 1e-6) / 1e12, 2)
                     st["fraction_of_8TBps_peak"] = round(nbytes[gamma] / (st["median_us"] * 1e-6) / PEAK_BPS, 3)
         res["fgla" if gamma == 1.0 else "general"] = entry

@@ -12,7 +12,7 @@ backward_ms           the backward sweep: 4 x specinv_cgla_step_adjoint, specinv
                       split of the cotangents between spec, known_spec and known_wave in torch ops
 composed_*_ms         the baseline: the same layer composed from si.gla_projection, si.istft, torch.where and element-wise torch
                       ops under autograd on the device, forward and backward
-step_kernel_ms        specinv_cgla_extrap_adjoint alone (k_cgla_step_adjoint + the finishing launch) and the bytes / s it achieves at
+step_kernel_ms        specinv_cgla_extrap_adjoint alone (k_agla_step_adjoint + the finishing launch) and the bytes / s it achieves at
                       12 (general) or 10 (every gamma = 1) transfers of 4 bytes plus one mask byte per sample
 No gate: the figures go into DESIGN 3.18.
 """
