@@ -189,6 +189,29 @@ enum { SPECINV_HPSS_COMPONENTS = 0, SPECINV_HPSS_MASKS = 1, SPECINV_HPSS_MEDIANS
 int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames, int32_t win_harm,
                  int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode, int32_t is_complex,
                  int32_t dtype, int32_t device, void* hip_stream);
+/* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
+ * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
+ * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept
+ * between calls.  With N = frame (even, 2 ... 2048), Hs = hop (the synthesis hop, 1 ... N), D = tol (0 ... 1024), w = window and
+ * xz(i) = x[i] for 0 <= i < n_in, else 0:
+ *     Frames.  M = n_frames = (n_out - 1 + N/2) / Hs + 1, exactly the frames whose support [m Hs - N/2, m Hs + N/2) meets [0, n_out).
+ *     Analysis centres.  a_m = centres[m], m < M: any non-decreasing int64 array (for a fixed rate the caller makes
+ *       floor(m Hs rate + 0.5) once in float64; the kernels never evaluate that expression).
+ *     Lag chain.  del_0 = 0; for m = 0 ... M - 2, with u_m = a_m + del_m - N/2:
+ *       p[n]      = xz(u_m + Hs + n), n < N                            (the natural continuation of frame m)
+ *       c[d]      = sum_n xz(a_{m+1} - N/2 + d + n) p[n], |d| <= D     (float64 products and sums for both dtypes)
+ *       del_{m+1} = the d with the largest c[d]; among equals the smallest |d|; of +-d the negative one
+ *     Overlap-add.  For 0 <= j < n_out, over the frames m in [0, M) with 0 <= n = j - m Hs + N/2 < N, in ascending m, in float64:
+ *       acc[j] = sum_m w[n] xz(u_m + n) ;  ow[j] = sum_m w[n] ;  y[j] = acc[j] / (ow[j] >= 1e-3 ? ow[j] : 1), rounded once.
+ * lags = del is always written, as zeros when tol == 0; the chain is not run when tol == 0 or n_frames == 1.  ow does not depend
+ * on the data.  Every read is guarded against [0, n_in): no centre and no lag can read outside a row.  Any batch: it is not a
+ * launch dimension of its own.  NaN input is unspecified.  Stateless: a running method is not disturbed.
+ * SPECINV_EINVAL, before the device is touched, in this order: a NULL pointer (x, centres, window, lags, y) ; y == x ; batch, n_in
+ * or n_out < 1 ; frame odd or outside 2 ... 2048 ; hop outside 1 ... frame ; tol outside 0 ... 1024 ;
+ * n_frames != (n_out - 1 + frame / 2) / hop + 1 ; an unknown dtype. */
+int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
+                  int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
+                  void* hip_stream);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

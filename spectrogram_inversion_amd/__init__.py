@@ -26,4 +26,5 @@ from .projection import gla_projection, stft, istft                     # noqa: 
 from .timescale import phase_vocoder, time_stretch, stretched_frames, pitch_shift   # noqa: E402,F401
 from .resample import resample                                          # noqa: E402,F401
 from .hpss import hpss, hpss_medians, hpss_audio, harmonic, percussive   # noqa: E402,F401
+from .tsm import wsola, ola, time_stretch_hpss                          # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

@@ -8,6 +8,7 @@
 #include "kernels_mel_nnls_adjoint.h"
 #include "kernels_hpss.h"
 #include "kernels_resample.h"
+#include "kernels_wsola.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -345,6 +346,33 @@ int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int3
                               margin_harm, margin_perc, out_mode, is_complex != 0, stream);
   return hpss_launch<double>((const double*)spec, (double*)out_a, (double*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
                              margin_harm, margin_perc, out_mode, is_complex != 0, stream);
+}
+int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
+                  int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
+                  void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(x && centres && window && lags && y, SPECINV_EINVAL, "specinv_wsola: NULL %s",
+           !x ? "x" : !centres ? "centres" : !window ? "window" : !lags ? "lags" : "y");
+  SI_CHECK(y != x, SPECINV_EINVAL, "specinv_wsola: y must not alias x");
+  SI_CHECK(batch >= 1 && n_in >= 1 && n_out >= 1, SPECINV_EINVAL,
+           "specinv_wsola: batch, n_in and n_out must be >= 1, got %lld, %lld and %lld", (long long)batch, (long long)n_in,
+           (long long)n_out);
+  SI_CHECK(frame >= 2 && frame <= kWsolaMaxFrame && !(frame & 1), SPECINV_EINVAL, "specinv_wsola: frame must be even in 2 ... %d, got %d",
+           kWsolaMaxFrame, frame);
+  SI_CHECK(hop >= 1 && hop <= frame, SPECINV_EINVAL, "specinv_wsola: hop must be in 1 ... frame = %d, got %d", frame, hop);
+  SI_CHECK(tol >= 0 && tol <= kWsolaMaxTol, SPECINV_EINVAL, "specinv_wsola: tol must be in 0 ... %d, got %d", kWsolaMaxTol, tol);
+  const __int128 want = ((__int128)n_out - 1 + frame / 2) / hop + 1;
+  SI_CHECK((__int128)n_frames == want, SPECINV_EINVAL, "specinv_wsola: n_frames is %d, %lld outputs at frame %d and hop %d take %lld",
+           n_frames, (long long)n_out, frame, hop, (long long)want);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (dtype == SPECINV_F32)
+    return wsola_launch<float>((const float*)x, centres, (const float*)window, lags, (float*)y, batch, n_in, n_out, n_frames, frame,
+                               hop, tol, stream);
+  return wsola_launch<double>((const double*)x, centres, (const double*)window, lags, (double*)y, batch, n_in, n_out, n_frames,
+                              frame, hop, tol, stream);
 }
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]) {
   ENTER(plan);
