@@ -212,6 +212,35 @@ int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int3
 int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
                   int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
                   void* hip_stream);
+/* Phase gradient heap integration in its real-time form with one look-ahead frame (RTPGHI, Prusa & Sondergaard 2016; not in the
+ * reference; csrc/kernels_pghi.h): a phase for magnitudes alone, in one launch.  mag (batch, n_freq, n_frames) real and non-negative
+ * -> spec_out (batch, n_freq, n_frames) complex = mag exp(i phi), interleaved (re, im) of `dtype`; optionally phase_out, the unwrapped
+ * float64 phi, and parents_out, int8 codes; device arrays on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  No
+ * plan: nothing is kept between calls.  Per item, with N = n_fft, a = hop, F = n_freq = N/2 + 1, T = n_frames, s[m,n] the
+ * magnitudes, g = gamma, all arithmetic float64 for both dtypes:
+ *     floor = tol * max(0, max s) ; (m,n) is live iff s > 0 and s >= floor ; l[m,n] = log(max(s, floor)), mirrored in frequency:
+ *       l[-1] = l[1], l[F] = l[F-2].  An item whose maximum is 0 has no live bin.
+ *     wt[m,n] = (2 pi / N) ((a m) mod N) + (a N / g) ((l[m+1,n] - l[m-1,n]) / 2)       (a m reduced as an integer)
+ *     wf[m,n] = pi - (g / (a N)) D[m,n] ;  D = (l[m,n+1] - l[m,n-1]) / 2 for 0 < n < T-1, l[m,1] - l[m,0] at n = 0,
+ *       l[m,T-1] - l[m,T-2] at n = T-1, 0 for T = 1      (the pi: frames start at sample 0, the window centre sits at N/2)
+ *     Frame n given frame n-1:  c[m] = s[m,n] if live else -inf ; p[m] = s[m,n-1] if (m,n-1) is live else -inf ; for n = 0 every
+ *       p[m] = -inf but for the lowest-index maximum of s[:,0], which has p = +inf if it is live.
+ *       Lf[0] = -inf, Lf[m] = min(c[m-1], max(p[m-1], Lf[m-1])) ;  Rg[F-1] = -inf, Rg[m] = min(c[m+1], max(p[m+1], Rg[m+1]))
+ *       Parent of a live bin, b = max(p[m], Lf[m], Rg[m]):  code 0 if p[m] >= b (time wins ties, and when all three are -inf),
+ *       else code 1 if Lf[m] >= b, else code 2 ; a bin that is not live has code 3.
+ *     phi:  code 0: phi[m,n-1] + (wt[m,n-1] + wt[m,n]) / 2, in frame 0 exactly 0 ;  code 1: phi[m-1,n] + (wf[m-1,n] + wf[m,n]) / 2 ;
+ *       code 2: phi[m+1,n] - (wf[m+1,n] + wf[m,n]) / 2 ;  code 3: 0, and that 0 is what a later time step reads.
+ *     spec_out = (s cos phi, s sin phi), evaluated in float64 and rounded once.
+ * This is the heap of RTPGHI (the heap holds frame n-1 with keys p, a popped bin sets its unset neighbours and pushes them with
+ * key c): a bin is set by the candidate with the widest max-min path, and min(c, max(p, .)) composes associatively.  Every decision
+ * compares input values exactly.  n_fft is even, 2 ... 5828 (SPECINV_EUNSUPPORTED above: the frame's state no longer fits a compute
+ * unit's LDS); any batch, it is not a launch dimension of its own.  NaN input is unspecified.  Stateless: a running method is not
+ * disturbed.  SPECINV_EINVAL, before the device is touched, in this order: NULL mag or spec_out ; spec_out == mag ; batch, n_freq or
+ * n_frames < 1 ; n_fft < 2 or odd, or n_freq != n_fft / 2 + 1 ; hop < 1 ; gamma not finite and positive ; tol outside (0, 1) ; an
+ * unknown dtype. */
+int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
+                 int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
+                 void* hip_stream);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

@@ -27,4 +27,5 @@ from .timescale import phase_vocoder, time_stretch, stretched_frames, pitch_shif
 from .resample import resample                                          # noqa: E402,F401
 from .hpss import hpss, hpss_medians, hpss_audio, harmonic, percussive   # noqa: E402,F401
 from .tsm import wsola, ola, time_stretch_hpss                          # noqa: E402,F401
+from .pghi import rtpghi                                                # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

@@ -132,8 +132,8 @@ struct eps16<double> {
 // coefficients, 2^-58): the float64 results are good to ~1e-16, rounded to float32 they equal the library's except where the
 // exact value sits within 1e-16 of a rounding boundary.  Phases beyond 1e9 rad (and NaN / inf) take the library path.
 __device__ inline void sincos_phase(double phi, double* sn, double* cs) { sincos(phi, sn, cs); }
-__device__ inline void sincos_phase(float phi_f, double* sn, double* cs) {
-  const double phi = (double)phi_f;
+// (the float64 body of the float32 overload, for a caller whose float64 phase stays moderate: k_pghi)
+__device__ inline void sincos_moderate(double phi, double* sn, double* cs) {
   if (!(fabs(phi) < 1.0e9)) {
     sincos(phi, sn, cs);
     return;
@@ -159,6 +159,7 @@ __device__ inline void sincos_phase(float phi_f, double* sn, double* cs) {
   *sn = (q & 2) ? -s1 : s1;
   *cs = ((q + 1) & 2) ? -c1 : c1;
 }
+__device__ inline void sincos_phase(float phi_f, double* sn, double* cs) { sincos_moderate((double)phi_f, sn, cs); }
 
 // wave-wide (64 lanes) sum in double
 __device__ inline double wave_sum(double v) {

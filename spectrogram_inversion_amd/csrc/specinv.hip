@@ -9,6 +9,7 @@
 #include "kernels_hpss.h"
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
+#include "kernels_pghi.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -373,6 +374,31 @@ int specinv_wsola(const void* x, const int64_t* centres, const void* window, int
                                hop, tol, stream);
   return wsola_launch<double>((const double*)x, centres, (const double*)window, lags, (double*)y, batch, n_in, n_out, n_frames,
                               frame, hop, tol, stream);
+}
+int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
+                 int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
+                 void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(mag && spec_out, SPECINV_EINVAL, "specinv_pghi: NULL %s", !mag ? "mag" : "spec_out");
+  SI_CHECK(spec_out != mag, SPECINV_EINVAL, "specinv_pghi: spec_out must not alias mag");
+  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
+           "specinv_pghi: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
+  SI_CHECK(n_fft >= 2 && !(n_fft & 1) && n_freq == n_fft / 2 + 1, SPECINV_EINVAL,
+           "specinv_pghi: n_fft must be even and n_freq = n_fft / 2 + 1, got n_fft %d and n_freq %d", n_fft, n_freq);
+  SI_CHECK(hop >= 1, SPECINV_EINVAL, "specinv_pghi: hop must be >= 1, got %d", hop);
+  SI_CHECK(gamma > 0 && gamma <= 1.7976931348623157e308, SPECINV_EINVAL, "specinv_pghi: gamma must be finite and > 0, got %g", gamma);
+  SI_CHECK(tol > 0 && tol < 1, SPECINV_EINVAL, "specinv_pghi: tol must be in (0, 1), got %g", tol);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(n_fft <= kPghiMaxFft, SPECINV_EUNSUPPORTED, "specinv_pghi: n_fft %d is beyond %d, where a frame's state fills the LDS",
+           n_fft, kPghiMaxFft);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (dtype == SPECINV_F32)
+    return pghi_launch<float>((const float*)mag, (cplx<float>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft, hop,
+                              gamma, tol, stream);
+  return pghi_launch<double>((const double*)mag, (cplx<double>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft,
+                             hop, gamma, tol, stream);
 }
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]) {
   ENTER(plan);
