@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from . import methods as _m
 from .autograd import _input_grad
 from .plan import args_helper, get_plan, require_gpu, trim_plan_cache
@@ -166,7 +167,7 @@ class _AglaUnfoldedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec3, alpha, beta, gamma, plan, n_iter):
         ctx.real_in = not spec3.is_complex()
-        start = spec3.detach().contiguous()
+        start = ingest(spec3, plan.device, plan.dtype if ctx.real_in else plan.cdtype)
         sched = [t.detach().tolist() for t in (alpha, beta, gamma)]
         if ctx.real_in:
             plan.agla_init_sched(None, start, *sched)              # phase_init on the device

@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .metrics import _from_sums
 
 
@@ -20,10 +21,10 @@ class _GriffinLimFn(torch.autograd.Function):
     def forward(ctx, spec3, plan, alpha, max_iter, tol, eva_iter, metric, on_eval):
         real_in = not spec3.is_complex()
         if real_in:
-            mag = spec3.detach().contiguous()
+            mag = ingest(spec3, plan.device, plan.dtype)
             c0 = plan.phase_init(mag)                                  # methods.py:106
         else:
-            c0 = spec3.detach().contiguous()
+            c0 = ingest(spec3, plan.device, plan.cdtype)
             mag = c0.abs().contiguous()                                # methods.py:110
         lr = alpha / (1.0 + alpha)                                     # :235
         p = c0
@@ -57,7 +58,7 @@ class _GriffinLimFn(torch.autograd.Function):
     def backward(ctx, g_y):
         plan, lr = ctx.plan, ctx.lr
         mag, c0, *spectra = ctx.saved_tensors
-        gx = g_y.detach().to(plan.dtype).contiguous()
+        gx = ingest(g_y, plan.device, plan.dtype)
         gm = torch.zeros_like(mag)
         gp = None
         for s_k in reversed(spectra):
@@ -74,7 +75,7 @@ class _GriffinLimFn(torch.autograd.Function):
 def _input_grad(ctx, plan, mag, c0, gc, gm):
     """Chain the cotangents of C0 (complex) and of the target magnitude back to the user's `spec`."""
     if ctx.real_in:
-        plan.phase_init_adjoint(mag, gc.contiguous(), gm)              # C0 = phase_init(mag)
+        plan.phase_init_adjoint(mag, ingest(gc, plan.device, plan.cdtype), gm)              # C0 = phase_init(mag)
         return gm
     absc = c0.abs()
     unit = torch.where(absc > 0, c0 / absc, torch.zeros_like(c0))
@@ -89,10 +90,10 @@ class _ADMMFn(torch.autograd.Function):
     def forward(ctx, spec3, plan, rho, max_iter, tol, eva_iter, metric, on_eval):
         real_in = not spec3.is_complex()
         if real_in:
-            mag = spec3.detach().contiguous()
+            mag = ingest(spec3, plan.device, plan.dtype)
             c0 = plan.phase_init(mag)
         else:
-            c0 = spec3.detach().contiguous()
+            c0 = ingest(spec3, plan.device, plan.cdtype)
             mag = c0.abs().contiguous()
         X, U = c0, torch.zeros_like(c0)                                # :458-460
         x = plan.istft(c0)                                             # :461
@@ -122,7 +123,7 @@ class _ADMMFn(torch.autograd.Function):
     def backward(ctx, g_y):
         plan, rho = ctx.plan, ctx.rho
         mag, c0, *spectra = ctx.saved_tensors
-        gx = g_y.detach().to(plan.dtype).contiguous()
+        gx = ingest(g_y, plan.device, plan.dtype)
         gm = torch.zeros_like(mag)
         gX = gU = None
         for v_k in reversed(spectra):
@@ -140,7 +141,7 @@ class _RtisiFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, spec3, plan, look_ahead, asym, max_iter, alpha):
-        mag = spec3.detach().contiguous()
+        mag = ingest(spec3, plan.device, plan.dtype)
         x, rec = plan.rtisi_recorded(mag, look_ahead, asym, max_iter, alpha)
         ctx.plan, ctx.cfg = plan, (look_ahead, asym, max_iter, alpha)
         ctx.save_for_backward(mag, rec)
@@ -149,7 +150,7 @@ class _RtisiFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_y):
         mag, rec = ctx.saved_tensors
-        gm = ctx.plan.rtisi_adjoint(mag, rec, g_y.detach().contiguous(), *ctx.cfg)
+        gm = ctx.plan.rtisi_adjoint(mag, rec, ingest(g_y, ctx.plan.device, ctx.plan.dtype), *ctx.cfg)
         return gm, None, None, None, None, None
 
 

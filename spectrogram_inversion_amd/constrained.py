@@ -18,6 +18,7 @@ import torch
 from tqdm import tqdm
 
 from . import _lib
+from ._ingest import ingest
 from . import methods as _m
 from .agla import _finish, _prepare, _schedules, _sweep, accelerated_griffin_lim, agla_unfolded
 from .autograd import _input_grad
@@ -188,7 +189,9 @@ class _CglaUnfoldedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec3, K, xk, alpha, beta, gamma, M, W, plan, n_iter):
         ctx.real_in = not spec3.is_complex()
-        start = spec3.detach().contiguous()
+        start = ingest(spec3, plan.device, plan.dtype if ctx.real_in else plan.cdtype)
+        if K is not None:
+            K = ingest(K, plan.device, plan.cdtype)
         sched = [t.detach().tolist() for t in (alpha, beta, gamma)]
         _begin(plan, start, K, M, xk, W, *sched)
         waves = []
@@ -199,7 +202,7 @@ class _CglaUnfoldedFn(torch.autograd.Function):
         plan.agla_constrain(None)
         ctx.plan, ctx.sched, ctx.M, ctx.W = plan, sched, M, W
         ctx.has_K = K is not None
-        ctx.save_for_backward(start, y, *waves, *(() if K is None else (K.detach(),)))
+        ctx.save_for_backward(start, y, *waves, *(() if K is None else (K,)))
         return y
 
     @staticmethod

@@ -40,6 +40,7 @@ import numbers
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .plan import _RECOGNISED, require_gpu
 
 __all__ = ["hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive"]
@@ -110,7 +111,7 @@ def _run(spec, sizes, power, margins, mode):
     device = require_gpu(spec.device)
     lib = _lib.load()
     work = (torch.complex64 if rdtype == torch.float32 else torch.complex128) if cplx else rdtype
-    s3 = spec.detach().reshape((-1,) + tuple(spec.shape[-2:])).to(device=device, dtype=work).contiguous()
+    s3 = ingest(spec.reshape((-1,) + tuple(spec.shape[-2:])), device, work)
     out_work = work if out_cplx else rdtype
     out_a = torch.empty(s3.shape, dtype=out_work, device=device)
     out_b = torch.empty(s3.shape, dtype=out_work, device=device)

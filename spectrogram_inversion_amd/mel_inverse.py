@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .agla import agla_unfolded
 from .methods import ADMM, RTISI_LA, _MAX_PLAN_BATCH, _slices, griffin_lim
 from .plan import _RECOGNISED, Plan, args_helper, get_plan, require_gpu, trim_plan_cache
@@ -166,7 +167,7 @@ class _MelNnlsUnfoldedFn(torch.autograd.Function):
             raise NotImplementedError(f"mel_to_stft_unfolded: {n_iter} iterations of a frame of {plan.n_freq} bins and {bank[0].shape[0]} "
                                       f"mel bands ({plan.dtype}) do not fit a CU's LDS in the backward pass: this shape admits "
                                       f"n_iter <= {most.value}")
-        y = mel3.detach().contiguous()
+        y = ingest(mel3, plan.device, plan.dtype)
         ctx.plan, ctx.bank, ctx.n_iter, ctx.power = plan, bank, n_iter, power
         ctx.save_for_backward(y)
         return _nnls(plan, *bank, y, n_iter, power)

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .methods import _MAX_PLAN_BATCH, _no_complex_window, _run_loop
 from .plan import Plan, args_helper, get_plan, require_gpu, trim_plan_cache
 
@@ -168,8 +169,8 @@ class _MisiUnfoldedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, specs4, mix2, plan, n_iter):
         B, K, F, T = specs4.shape
-        specs3 = specs4.detach().reshape(B * K, F, T).contiguous()
-        mix = mix2.detach().contiguous()
+        specs3 = ingest(specs4.reshape(B * K, F, T), plan.device, plan.cdtype if specs4.is_complex() else plan.dtype)
+        mix = ingest(mix2, plan.device, plan.dtype)
         init, mag = _start(plan, specs3, mix, K)
         plan.misi_init(init, mag, mix, K)
         waves = []

@@ -47,6 +47,7 @@ import numbers
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .plan import args_helper, require_gpu
 
 __all__ = ["rtpghi", "HANN_GAMMA", "HAMMING_GAMMA"]
@@ -125,7 +126,7 @@ def rtpghi(spec, gamma=None, tol=1e-6, return_phase=False, return_parents=False,
         return res[0] if len(res) == 1 else tuple(res)
     device = require_gpu(spec.device)
     lib = _lib.load()
-    s3 = spec.detach().reshape(shape3).to(device=device, dtype=dtype).contiguous()
+    s3 = ingest(spec.reshape(shape3), device, dtype)
     out = torch.empty(s3.shape, dtype=cdtype, device=device)
     phase = torch.empty(s3.shape, dtype=torch.float64, device=device) if return_phase else None
     parents = torch.empty(s3.shape, dtype=torch.int8, device=device) if return_parents else None

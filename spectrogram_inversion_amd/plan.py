@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._ingest import ingest
 
 _REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64, torch.complex32: torch.float16}
 _CPLX = {torch.float32: torch.complex64, torch.float64: torch.complex128}
@@ -138,10 +139,9 @@ class Plan:
         _lib.check(self.lib.specinv_plan_set_stream(self._h, C.c_void_p(s.cuda_stream)))
 
     def _in(self, t: torch.Tensor, dtype, shape=None):
-        # (the optimiser loops call this a few hundred thousand times with tensors that are already in place: skip the three
-        # dispatcher round trips then)
-        if t.dtype != dtype or t.device != self.device or t.requires_grad or not t.is_contiguous():
-            t = t.detach().to(device=self.device, dtype=dtype).contiguous()
+        # (the optimiser loops call this a few hundred thousand times with tensors that are already in place: `ingest` hands those
+        # back after attribute tests alone, without a dispatcher round trip)
+        t = ingest(t, self.device, dtype)
         if shape is not None:
             assert tuple(t.shape) == tuple(shape), f"expected shape {tuple(shape)}, got {tuple(t.shape)}"
         return t

@@ -20,6 +20,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import methods as _m
+from ._ingest import ingest
 from .plan import args_helper, get_plan, require_gpu, trim_plan_cache
 
 __all__ = ["gla_projection", "stft", "istft"]
@@ -67,7 +68,7 @@ class _ProjectionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mag_fm, plan):
-        x, mag_fm = x.detach().contiguous(), mag_fm.detach().contiguous()
+        x, mag_fm = ingest(x, plan.device, plan.dtype), ingest(mag_fm, plan.device, plan.dtype)
         ctx.plan = plan
         ctx.save_for_backward(x, mag_fm)
         return plan.project(x, mag_fm)

@@ -23,6 +23,7 @@ import math
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .plan import require_gpu
 
 __all__ = ["resample"]
@@ -84,7 +85,7 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     device = require_gpu(x.device)
     lib = _lib.load()
     dtype = _REAL[x.dtype]
-    x2 = x.detach().reshape(-1, n_in).to(device=device, dtype=dtype).contiguous()
+    x2 = ingest(x.reshape(-1, n_in), device, dtype)
     out = torch.empty((x2.shape[0], n_out), dtype=dtype, device=device)
     stream = torch.cuda.current_stream(device)
     _lib.check(lib.specinv_resample(x2.data_ptr(), out.data_ptr(), x2.shape[0], n_in, n_out, o, n, width, rolloff,

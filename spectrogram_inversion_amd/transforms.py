@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .plan import Plan, StftArgs, require_gpu
 
 
@@ -66,7 +67,8 @@ class DeviceTransform:
         """Returns (forward(x), loss_and_grad(x)) closures for the optimiser."""
         x2 = x.reshape(1, -1) if x.dim() == 1 else x
         plan = self._plan(x2)
-        tgt = target.reshape(plan.batch, plan.n_out, plan.n_frames)
+        # (dense once, here: the closures below hand it to the plan at every evaluation)
+        tgt = ingest(target.reshape(plan.batch, plan.n_out, plan.n_frames), plan.device, plan.dtype)
 
         def fwd(v):
             return plan.transform_forward(v.reshape(x2.shape))

@@ -53,6 +53,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._ingest import ingest
 from .plan import require_gpu
 from .timescale import _METHODS, _checked_rate
 
@@ -135,9 +136,9 @@ def _run(x, rate, n, hop, tol, window, length, return_lags, what):
     device = require_gpu(x.device)
     lib = _lib.load()
     dtype = _REAL[x.dtype]
-    x2 = x.detach().reshape(-1, n_in).to(device=device, dtype=dtype).contiguous()
+    x2 = ingest(x.reshape(-1, n_in), device, dtype)
     # (the default window is made on the CPU: the same bits on every device, and those a caller's own hann_window(N) has)
-    w = (torch.hann_window(n, dtype=dtype) if window is None else window.detach()).to(device=device, dtype=dtype).contiguous()
+    w = ingest(torch.hann_window(n, dtype=dtype) if window is None else window, device, dtype)
     centres = torch.from_numpy(wsola_centres(n_frames, hop, rate)).to(device)
     y = torch.empty((x2.shape[0], n_out), dtype=dtype, device=device)
     lags = torch.empty((x2.shape[0], n_frames), dtype=torch.int32, device=device)
