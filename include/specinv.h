@@ -241,6 +241,32 @@ int specinv_wsola(const void* x, const int64_t* centres, const void* window, int
 int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
                  int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
                  void* hip_stream);
+/* Consistent Wiener filtering (Le Roux & Vincent, IEEE SPL 2013; not in the reference; csrc/kernels_cwf.h): the
+ * whole loop on the plan's stream.  mix, S_out, N_out are (batch, n_freq, n_frames) complex as specinv_stft writes them; var_s,
+ * var_n are (batch, n_freq, n_frames) real and >= 0, all device arrays of the plan's dtype at 16-byte aligned addresses.  Per
+ * item, with X = mix, v_s = var_s, v_n = var_n, a = hop_length, N = n_fft; every scalar and sum is float64 for both dtypes, the
+ * arrays are held in the plan's dtype:
+ *     m = floor * max(v_s + v_n) ; m == 0: the item's S is 0 and it takes no part ; v_s, v_n <- max(v_s, m), max(v_n, m)
+ *     Lam = 1 / v_s + 1 / v_n ;  g = gamma / mean(v_s v_n / (v_s + v_n)) if relative, else gamma
+ *     G Z = specinv_stft(specinv_istft(Z)) ;  G' U = specinv_istft_adjoint(specinv_stft_adjoint(U)), the real adjoint of G under
+ *       <a, b> = sum Re a Re b + Im a Im b over the item's bins, unweighted
+ *     A P = Lam P + g (u - G' u), u = P - G P ;  M = Lam + g (1 - a / N)
+ *     S_0 = v_s / (v_s + v_n) X ;  r = X / v_n - A S_0 ;  z = r / M ;  p = z ;  rz = <r, z> ;  rz0 = rz
+ *     n_iter times:  q = A p ; alpha = rz / <p, q> ; S += alpha p ; r -= alpha q ; z = r / M ; rz' = <r, z> ; beta = rz' / rz ;
+ *       p = z + beta p ; rz = rz'
+ *     an item whose rz is 0 or whose <p, q> is not > 0 is finished: alpha = beta = 0 from then on.
+ * S_out is the last iterate - preconditioned conjugate gradients on A S = X / v_n, the stationarity condition of
+ * sum |X - S|^2 / v_n + |S|^2 / v_s + g |S - G S|^2 - and N_out = X - S_out, formed once at the end; N_out is the loop's scratch
+ * until then.  An item's result does not depend on the other items, alpha and beta never visit the host, no atomics: two calls give
+ * the same bits.  tol > 0: the residuals sqrt(rz / rz0) (0 for a finished item) are read back after every eva_iter-th iteration and
+ * the loop stops when every item's is <= tol; tol == 0: nothing is read back before the end.  residual_out_host (batch doubles, or
+ * NULL: no read-back at all) receives the final residuals, *iters_out (or NULL) the iterations run.  Stateless: scratch only (three
+ * spectra, Lam and one signal, kept by the plan for the next call), a running method is not disturbed.  SPECINV_EINVAL, before the
+ * device is touched, in this order: a NULL array (mix, var_s, var_n, S_out, N_out) ; an output that aliases the other or an input ;
+ * an array off a 16-byte boundary ; gamma not finite and positive ; floor outside (0, 1) ; n_iter < 0 ; eva_iter < 1 ; tol < 0 or
+ * NaN ; a NULL plan.  SPECINV_EUNSUPPORTED: a two-sided plan. */
+int specinv_cwf_run(specinv_plan* plan, const void* mix, const void* var_s, const void* var_n, double gamma, int relative, double floor,
+                    int n_iter, int eva_iter, double tol, void* S_out, void* N_out, double* residual_out_host, int* iters_out);
 /* metrics.py sums over n elements of two real device arrays of the plan's dtype */
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]);
 

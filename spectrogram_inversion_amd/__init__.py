@@ -28,4 +28,5 @@ from .resample import resample                                          # noqa: 
 from .hpss import hpss, hpss_medians, hpss_audio, harmonic, percussive   # noqa: E402,F401
 from .tsm import wsola, ola, time_stretch_hpss                          # noqa: E402,F401
 from .pghi import rtpghi                                                # noqa: E402,F401
+from .wiener import consistent_wiener, consistent_wiener_audio          # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

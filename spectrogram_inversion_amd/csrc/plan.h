@@ -15,6 +15,12 @@ struct MelNnlsFree {
   void operator()(MelNnlsState* st) const;
 };
 
+// the buffers of specinv_cwf_run (tu_cwf.hip owns their layout): scratch, nothing is kept between calls
+struct CwfState;
+struct CwfFree {
+  void operator()(CwfState* st) const;
+};
+
 // Type-erased interface; PlanT<float> / PlanT<double> implement it (plan_impl.h).
 struct PlanBase {
   specinv_stft_cfg cfg{};
@@ -29,6 +35,7 @@ struct PlanBase {
   int64_t dev_bytes = 0;   // device memory held by the plan's buffers (account_bytes)
   int objective_kind = -1;   // what the last transform_loss_grad ran (specinv_transform_objective_kind)
   std::unique_ptr<MelNnlsState, MelNnlsFree> mel_nnls;   // filterbank in band form + momentum table (specinv_mel_nnls_setup)
+  std::unique_ptr<CwfState, CwfFree> cwf;   // r, p, u, Lam, a signal and the partial sums of specinv_cwf_run, made by its first call
 
   virtual ~PlanBase() = default;
   virtual int setup() = 0;
@@ -141,6 +148,10 @@ std::unique_ptr<PlanBase> make_plan_f32();
 std::unique_ptr<PlanBase> make_plan_f64();
 
 double metric_from_sums(int metric, const double sums[4]);
+
+// consistent Wiener filtering on the plan's four transforms (tu_cwf.hip; kernels_cwf.h); stateless: scratch only
+int cwf_run(PlanBase& plan, const void* mix, const void* var_s, const void* var_n, double gamma, bool relative, double floor,
+            int n_iter, int eva_iter, double tol, void* S_out, void* N_out, double* residual_out_host, int* iters_out);
 
 }  // namespace specinv
 

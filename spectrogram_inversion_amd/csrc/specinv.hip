@@ -400,6 +400,26 @@ int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* par
   return pghi_launch<double>((const double*)mag, (cplx<double>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft,
                              hop, gamma, tol, stream);
 }
+int specinv_cwf_run(specinv_plan* plan, const void* mix, const void* var_s, const void* var_n, double gamma, int relative, double floor,
+                    int n_iter, int eva_iter, double tol, void* S_out, void* N_out, double* residual_out_host, int* iters_out) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(mix && var_s && var_n && S_out && N_out, SPECINV_EINVAL, "specinv_cwf_run: NULL %s",
+           !mix ? "mix" : !var_s ? "var_s" : !var_n ? "var_n" : !S_out ? "S_out" : "N_out");
+  SI_CHECK(S_out != N_out && S_out != mix && N_out != mix && S_out != var_s && S_out != var_n && N_out != var_s && N_out != var_n,
+           SPECINV_EINVAL, "specinv_cwf_run: %s", S_out == N_out ? "N_out must not alias S_out" : "an output must not alias an input");
+  SI_CHECK(!(((uintptr_t)mix | (uintptr_t)var_s | (uintptr_t)var_n | (uintptr_t)S_out | (uintptr_t)N_out) & 15), SPECINV_EINVAL,
+           "specinv_cwf_run: the arrays must be 16-byte aligned");
+  SI_CHECK(gamma > 0 && std::isfinite(gamma), SPECINV_EINVAL, "specinv_cwf_run: gamma must be finite and > 0, got %g", gamma);
+  SI_CHECK(floor > 0 && floor < 1, SPECINV_EINVAL, "specinv_cwf_run: floor must be in (0, 1), got %g", floor);
+  SI_CHECK(n_iter >= 0, SPECINV_EINVAL, "specinv_cwf_run: n_iter must be >= 0, got %d", n_iter);
+  SI_CHECK(eva_iter >= 1, SPECINV_EINVAL, "specinv_cwf_run: eva_iter must be >= 1, got %d", eva_iter);
+  SI_CHECK(tol >= 0, SPECINV_EINVAL, "specinv_cwf_run: tol must be >= 0, got %g", tol);
+  PLAN_OR_FAIL(plan);
+  SI_CHECK(plan->impl->cfg.onesided, SPECINV_EUNSUPPORTED, "specinv_cwf_run takes one-sided spectrograms only");
+  ENTER(plan);
+  return cwf_run(*plan->impl, mix, var_s, var_n, gamma, relative != 0, floor, n_iter, eva_iter, tol, S_out, N_out, residual_out_host,
+                 iters_out);
+}
 int specinv_metric_sums(specinv_plan* plan, const void* a, const void* b, int64_t n, double sums_host[4]) {
   ENTER(plan);
   SI_CHECK(sums_host, SPECINV_EINVAL, "sums_host is NULL");
