@@ -241,6 +241,36 @@ int specinv_wsola(const void* x, const int64_t* centres, const void* window, int
 int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
                  int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
                  void* hip_stream);
+/* The phase vocoder with heap-integrated phase (Prusa & Holighaus 2017, "phase vocoder done right", in specinv_phase_vocoder's
+ * frame-resampling form; not in the reference; csrc/kernels_pvoc_pghi.h), in one launch.  spec_in (batch, n_freq,
+ * n_frames_in) complex, one-sided, -> spec_out (batch, n_freq, n_frames_out) complex, interleaved (re, im) of `dtype`; optionally
+ * parents_out, int8 codes of spec_out's shape; device arrays on HIP device `device`, enqueued on hip_stream (NULL: the null stream).
+ * No plan: nothing is kept between calls.  Per item, with t_j = (double)j * rate, i = floor(t_j), a = t_j - i, S0 = S[i],
+ * S1 = S[i+1] (frames at and beyond n_frames_in are +0 + 0i), adv = 2 pi k hop / n_fft, wrap(x) = x - 2 pi round(x / 2 pi),
+ * d_j = wrap(arg S1 - arg S0 - adv) + adv as for specinv_phase_vocoder; theta0 = arg S0 and theta1 = arg S1 are taken in `dtype`
+ * and widened, everything after them is float64 for both dtypes with no contraction:
+ *     q(z) = re re + im im from the input's own bits ;  r(z) = sqrt(q(z)) ;  m_j[k] = fl(fl(a r(S1[k])) + fl(fl(1 - a) r(S0[k])))
+ *     floor = tol * sqrt(max q over the item's input) ;  (j,k) is live iff m_j[k] > 0 and m_j[k] >= floor
+ *     Frame 0:  psi_0 = theta0 ;  code 0 where live, 3 elsewhere.
+ *     Frame j >= 1:  c[k] = m_j[k] if live else -inf ;  p[k] = m_{j-1}[k] if (j-1,k) is live else -inf ;
+ *       Lf[0] = -inf, Lf[k] = min(c[k-1], max(p[k-1], Lf[k-1])) ;  Rg[F-1] = -inf, Rg[k] = min(c[k+1], max(p[k+1], Rg[k+1]))
+ *       Parent of a live bin, b = max(p[k], Lf[k], Rg[k]):  code 0 if p[k] >= b (time wins ties, and when all three are -inf),
+ *       else code 1 if Lf[k] >= b, else code 2 ; a bin that is not live has code 3.
+ *       phi_j[k] = psi_{j-1}[k] + d_{j-1}[k] for every bin, one addition.
+ *       root(k) = k for codes 0 and 3 ; root(k+1) for code 2 (resolved first) ; root(k-1) for code 1.
+ *       psi_j[k] = phi_j[k] if root(k) = k, else (phi_j[root] - theta0_j[root]) + theta0_j[k], in that association.
+ *     spec_out[j][k] = (m cos psi, m sin psi), evaluated in float64 and rounded once.
+ * This is the per-frame heap of RTPGHI (specinv_pghi) with the analysis phase differences as the gradients: the frequency steps
+ * along a chain telescope to theta0[k] - theta0[root].  A bin that is not live keeps its own time-propagated phase and is never a
+ * parent; a silent item gives exact zeros.  |spec_out| may differ from specinv_phase_vocoder's by one rounding (that entry forms |z|
+ * with fma and hypot).  n_freq <= 2915 (SPECINV_EUNSUPPORTED above); any batch, it is not a launch dimension of its own.  float64
+ * input whose q over- or underflows (|z| beyond about 1e150 or below 1e-150) and NaN input are unspecified.  Stateless: a running
+ * method is not disturbed.  SPECINV_EINVAL, before the device is touched, in this order: NULL spec_in or spec_out ; spec_out ==
+ * spec_in ; batch, n_freq, n_frames_in, n_frames_out or n_fft < 1 ; n_freq != n_fft / 2 + 1 ; hop < 1 ; rate not finite and
+ * positive ; n_frames_out != the smallest n >= 1 with (double)n * rate >= n_frames_in ; tol outside (0, 1) ; an unknown dtype. */
+int specinv_pvoc_pghi(const void* spec_in, void* spec_out, int8_t* parents_out, int64_t batch, int32_t n_freq, int32_t n_frames_in,
+                      int32_t n_frames_out, int32_t n_fft, int32_t hop, double rate, double tol, int32_t dtype, int32_t device,
+                      void* hip_stream);
 /* Consistent Wiener filtering (Le Roux & Vincent, IEEE SPL 2013; not in the reference; csrc/kernels_cwf.h): the
  * whole loop on the plan's stream.  mix, S_out, N_out are (batch, n_freq, n_frames) complex as specinv_stft writes them; var_s,
  * var_n are (batch, n_freq, n_frames) real and >= 0, all device arrays of the plan's dtype at 16-byte aligned addresses.  Per

@@ -84,6 +84,8 @@ SIGNATURES = {
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,
                                _P]),
+    "specinv_pvoc_pghi": (C.c_int, [_P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32,
+                                    C.c_int32, _P]),
     "specinv_cwf_run": (C.c_int, [_P, _P, _P, _P, _D, C.c_int, _D, C.c_int, C.c_int, _D, _P, _P, _DP, _IP]),
     "specinv_metric_sums": (C.c_int, [_P, _P, _P, _I64, _DP]),
     "specinv_gla_init": (C.c_int, [_P, _P, _P, _D]),

@@ -10,6 +10,7 @@
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
 #include "kernels_pghi.h"
+#include "kernels_pvoc_pghi.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -399,6 +400,35 @@ int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* par
                               gamma, tol, stream);
   return pghi_launch<double>((const double*)mag, (cplx<double>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft,
                              hop, gamma, tol, stream);
+}
+int specinv_pvoc_pghi(const void* spec_in, void* spec_out, int8_t* parents_out, int64_t batch, int32_t n_freq, int32_t n_frames_in,
+                      int32_t n_frames_out, int32_t n_fft, int32_t hop, double rate, double tol, int32_t dtype, int32_t device,
+                      void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec_in && spec_out, SPECINV_EINVAL, "specinv_pvoc_pghi: NULL %s", !spec_in ? "spec_in" : "spec_out");
+  SI_CHECK(spec_out != spec_in, SPECINV_EINVAL, "specinv_pvoc_pghi: spec_out must not alias spec_in");
+  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames_in >= 1 && n_frames_out >= 1 && n_fft >= 1, SPECINV_EINVAL,
+           "specinv_pvoc_pghi: batch, n_freq, n_frames_in, n_frames_out and n_fft must be >= 1, got %lld, %d, %d, %d and %d",
+           (long long)batch, n_freq, n_frames_in, n_frames_out, n_fft);
+  SI_CHECK(n_freq == n_fft / 2 + 1, SPECINV_EINVAL,
+           "specinv_pvoc_pghi: one-sided spectra only, n_freq = n_fft / 2 + 1; got n_fft %d and n_freq %d", n_fft, n_freq);
+  SI_CHECK(hop >= 1, SPECINV_EINVAL, "specinv_pvoc_pghi: hop must be >= 1, got %d", hop);
+  SI_CHECK(rate > 0 && std::isfinite(rate), SPECINV_EINVAL, "specinv_pvoc_pghi: rate must be finite and > 0, got %g", rate);
+  const int64_t want = pvoc_stretched_frames(n_frames_in, rate);
+  SI_CHECK(want == (int64_t)n_frames_out, SPECINV_EINVAL, "specinv_pvoc_pghi: n_frames_out is %d, %d frames at rate %g stretch to %lld",
+           n_frames_out, n_frames_in, rate, (long long)want);
+  SI_CHECK(tol > 0 && tol < 1, SPECINV_EINVAL, "specinv_pvoc_pghi: tol must be in (0, 1), got %g", tol);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(n_freq <= kPghiMaxFreq, SPECINV_EUNSUPPORTED, "specinv_pvoc_pghi: n_freq %d is beyond %d, the bins a workgroup holds", n_freq,
+           kPghiMaxFreq);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (dtype == SPECINV_F32)
+    return pvoc_pghi_launch<float>((const cplx<float>*)spec_in, (cplx<float>*)spec_out, parents_out, batch, n_freq, n_frames_in,
+                                   n_frames_out, n_fft, hop, rate, tol, stream);
+  return pvoc_pghi_launch<double>((const cplx<double>*)spec_in, (cplx<double>*)spec_out, parents_out, batch, n_freq, n_frames_in,
+                                  n_frames_out, n_fft, hop, rate, tol, stream);
 }
 int specinv_cwf_run(specinv_plan* plan, const void* mix, const void* var_s, const void* var_n, double gamma, int relative, double floor,
                     int n_iter, int eva_iter, double tol, void* S_out, void* N_out, double* residual_out_host, int* iters_out) {

@@ -17,6 +17,10 @@ The vocoder's output is far from a consistent spectrogram (|STFT(ISTFT(P))| miss
     y = si.time_stretch(x, 0.8, n_fft=1024, hop_length=256, window=w)                  # 25 % longer
     P = si.phase_vocoder(si.stft(x, 1024, hop_length=256, window=w), 0.8, hop_length=256, window=w)
 
+`phase_lock="identity"` (csrc/kernels_pvoc_lock.h) and `phase_lock="pghi"` (csrc/kernels_pvoc_pghi.h) keep the
+phase coherent across the bins of a frame: around the nearest spectral peak, or along the magnitude-ordered heap of "phase vocoder
+done right" (Prusa & Holighaus 2017), which also helps on noisy and transient input.
+
 `pitch_shift` is the other half of the pair (`librosa.effects.pitch_shift`, `torchaudio.functional.pitch_shift`): `time_stretch` by
 2^(-n_steps / bins_per_octave), then `resample` (resample.py) back to the original rate and length.
 
@@ -26,13 +30,16 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 import math
 import numbers
 
 import torch
 
+from . import _lib
 from . import methods as _m
+from ._ingest import ingest
 from .plan import _RECOGNISED, args_helper, get_plan, require_gpu, trim_plan_cache
 from .projection import _COMPLEX, _check_items
 
@@ -40,6 +47,8 @@ __all__ = ["phase_vocoder", "time_stretch", "stretched_frames", "pitch_shift"]
 
 _METHODS = ("accelerated_griffin_lim", "griffin_lim", "ADMM")
 _MAX_FRAMES = 2147483000
+_LOCKS = ("identity", "pghi")
+_PGHI_MAX_FREQ = 2915         # the bins a workgroup of the "pghi" kernel holds: rtpghi's bound
 
 
 def _checked_rate(rate):
@@ -69,27 +78,67 @@ def stretched_frames(n_frames, rate):
 
 
 def _checked_lock(phase_lock):
-    if phase_lock is not None and not (isinstance(phase_lock, str) and phase_lock == "identity"):
-        raise ValueError(f"phase_lock must be None or 'identity', got {phase_lock!r}")
+    if phase_lock is not None and not (isinstance(phase_lock, str) and phase_lock in _LOCKS):
+        raise ValueError(f"phase_lock must be None, 'identity' or 'pghi', got {phase_lock!r}")
     return phase_lock
 
 
-def phase_vocoder(spec, rate, phase_lock=None, **stft_kwargs):
+def _checked_lock_tol(lock_tol):
+    if isinstance(lock_tol, bool) or not isinstance(lock_tol, numbers.Real) or not 0 < lock_tol < 1:
+        raise ValueError(f"lock_tol must be a finite number in (0, 1), got {lock_tol!r}")
+    return float(lock_tol)
+
+
+def _pvoc_pghi(spec3, rate, n_out, lock_tol, return_parents, stft_kwargs):
+    """`phase_lock="pghi"` on (B, F, T), B >= 1: `specinv_pvoc_pghi`, stateless - no plan is made."""
+    args = args_helper(spec3, **stft_kwargs)
+    if not args.onesided:
+        raise NotImplementedError("phase_lock='pghi' takes one-sided spectrograms only")
+    if spec3.shape[1] > _PGHI_MAX_FREQ:
+        raise NotImplementedError(f"phase_lock='pghi': {spec3.shape[1]} bins are beyond the kernel's limit of {_PGHI_MAX_FREQ}")
+    device = require_gpu(spec3.device)
+    lib = _lib.load()
+    real = spec3.real.dtype
+    s = ingest(spec3, device, spec3.dtype)
+    out = torch.empty((s.shape[0], s.shape[1], n_out), dtype=s.dtype, device=device)
+    parents = torch.empty(out.shape, dtype=torch.int8, device=device) if return_parents else None
+    stream = torch.cuda.current_stream(device)
+    _lib.check(lib.specinv_pvoc_pghi(s.data_ptr(), out.data_ptr(), parents.data_ptr() if return_parents else None, s.shape[0],
+                                     s.shape[1], s.shape[2], n_out, args.n_fft, args.hop_length, rate, lock_tol,
+                                     _lib.F32 if real == torch.float32 else _lib.F64, stream.device.index,
+                                     C.c_void_p(stream.cuda_stream)))
+    return out, parents
+
+
+def phase_vocoder(spec, rate, phase_lock=None, lock_tol=1e-6, return_parents=False, **stft_kwargs):
     r"""A complex spectrogram (F, T) / (B, F, T) resampled along time by the phase vocoder: (F, T_out) / (B, F, T_out) complex of
     the same dtype and device, `T_out = stretched_frames(T, rate)`.  `rate > 1` shortens, `rate < 1` lengthens.
 
     `**stft_kwargs` are those the spectrogram was computed with, as everywhere (`hop_length` and `onesided` are what is read).
     The phase is accumulated in float64 for every dtype and the result rounded once; complex32 is computed as complex64 and
     rounded back.  A CPU tensor is computed on the current HIP device and comes back to the CPU.  Frames beyond the last read as
-    zeros, as in librosa and torchaudio.  Not differentiable.  At most 65535 items.
+    zeros, as in librosa and torchaudio.  Not differentiable.  At most 65535 items (any number with `phase_lock="pghi"`).
 
     `phase_lock=None` moves every bin's phase on its own.  `phase_lock="identity"` is identity phase locking (Laroche & Dolson
     1999; csrc/kernels_pvoc_lock.h): a bin is a peak of its frame when its squared magnitude exceeds that of its
     four neighbours, every bin follows the nearest peak, and around a peak the phase differences of the analysis frame are kept.
     The magnitude is the same.  On tonal input the locked result is two to seven times closer to a consistent spectrogram before
     any iteration; on noise it gains little and can lose.  One more launch, and batch * F * T_out doubles held by the plan.
+
+    `phase_lock="pghi"` is the phase vocoder with heap-integrated phase (Prusa & Holighaus 2017, "phase vocoder done right";
+    csrc/kernels_pvoc_pghi.h): identity locking in which a bin follows the root of its magnitude-ordered heap chain
+    - a bin is a root when its own magnitude in the previous output frame beats the widest path from its neighbours - and a root
+    continues from the locked phase of the previous output frame.  It helps on noisy and transient input too, where identity
+    locking does not.  Bins below `lock_tol` (finite, 0 < lock_tol < 1; read by this mode only) times the item's largest input
+    magnitude keep their own phase and own no other bin.  One launch, no plan, any number of items; one-sided spectrograms of
+    at most 2915 bins; the magnitude is formed as sqrt(re^2 + im^2) and may differ from the other modes' by one rounding.
+    `return_parents=True` (this mode only) returns `(P, parents)`, `parents` int8 of P's shape: 0 the bin's own previous frame,
+    1 from bin k - 1, 2 from bin k + 1, 3 below the floor.
     """
     _checked_lock(phase_lock)
+    lock_tol = _checked_lock_tol(lock_tol)
+    if return_parents and phase_lock != "pghi":
+        raise ValueError("return_parents is valid only with phase_lock='pghi'")
     if not isinstance(spec, torch.Tensor):
         raise TypeError("spec must be a torch.Tensor")
     if spec.dtype not in _COMPLEX:
@@ -102,9 +151,21 @@ def phase_vocoder(spec, rate, phase_lock=None, **stft_kwargs):
     spec3 = spec.unsqueeze(0) if spec.dim() == 2 else spec
     if spec3.shape[1] < 1 or spec3.shape[2] < 1:
         raise ValueError(f"spec of shape {tuple(spec.shape)} holds no frames")
-    _check_items(spec3.shape[0], "phase_vocoder", f"spec of shape {tuple(spec.shape)}")
+    if phase_lock != "pghi":                                   # (no plan there: the grid loops over any number of items)
+        _check_items(spec3.shape[0], "phase_vocoder", f"spec of shape {tuple(spec.shape)}")
     n_out = stretched_frames(spec3.shape[2], rate)
     spec3, stft_kwargs, half = _m._widen(spec3, stft_kwargs)
+    if phase_lock == "pghi":
+        if spec3.shape[0] == 0:
+            out, parents = spec.new_zeros((0, spec3.shape[1], n_out)), spec.new_zeros((0, spec3.shape[1], n_out), dtype=torch.int8)
+        else:
+            out, parents = _pvoc_pghi(spec3.detach(), rate, n_out, lock_tol, bool(return_parents), stft_kwargs)
+            if spec.dim() == 2:
+                out = out.squeeze(0)
+                parents = parents.squeeze(0) if return_parents else None
+            out = out.to(spec.device)
+            out = out.to(torch.complex32) if half else out
+        return (out, parents.to(spec.device)) if return_parents else out
     args = args_helper(spec3, **stft_kwargs)
     if spec3.shape[0] == 0:
         return spec.new_zeros((0, spec3.shape[1], n_out))
@@ -122,19 +183,20 @@ def phase_vocoder(spec, rate, phase_lock=None, **stft_kwargs):
     return out.to(torch.complex32) if half else out
 
 
-def time_stretch(x, rate, n_fft=None, max_iter=32, method="accelerated_griffin_lim", phase_lock=None, **kwargs):
+def time_stretch(x, rate, n_fft=None, max_iter=32, method="accelerated_griffin_lim", phase_lock=None, lock_tol=1e-6, **kwargs):
     r"""A waveform (L,) / (B, L) played `rate` times as fast at the same pitch: a waveform of about L / rate samples.
 
     It is exactly
 
-        method(phase_vocoder(stft(x, n_fft, **stft_kwargs), rate, phase_lock, **stft_kwargs), max_iter=max_iter, **kwargs)
+        method(phase_vocoder(stft(x, n_fft, **stft_kwargs), rate, phase_lock, lock_tol, **stft_kwargs), max_iter=max_iter, **kwargs)
 
     with `method` one of "accelerated_griffin_lim" (the default: Fast Griffin-Lim at its default parameters), "griffin_lim" and
     "ADMM", started from the vocoder's phase with the vocoder's magnitude as the target.  `**kwargs` holds the STFT arguments
     (`hop_length`, `window`, `win_length`, `center`, ...; `n_fft` defaults as in `stft`) and whatever else the method takes
     (`tol`, `verbose`, `eva_iter`, `alpha`, ...), each with the method's own default.  `max_iter=0` is `istft` of the vocoder's
     output, the classic phase vocoder; with `phase_lock="identity"` (see `phase_vocoder`) that is usable on tonal material.  Locking
-    is worth the first few iterations there; after five or more the two starts end within 13 % of each other.
+    is worth the first few iterations there; after five or more the two starts end within 13 % of each other.  `phase_lock="pghi"`
+    with its `lock_tol` is the heap-integrated vocoder, which gives the better start on noisy and transient material as well.
 
     The result holds the samples `istft` gives `stretched_frames(T, rate)` frames, (T_out - 1) * hop_length with `center=True`: it
     is not padded or trimmed to round(L / rate).  dtype and device rules are those of `stft` and the method.
@@ -144,10 +206,11 @@ def time_stretch(x, rate, n_fft=None, max_iter=32, method="accelerated_griffin_l
         raise ValueError(f"method must be one of {', '.join(_METHODS)}, got {method!r}")
     rate = _checked_rate(rate)
     _checked_lock(phase_lock)
+    lock_tol = _checked_lock_tol(lock_tol)
     if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
         raise ValueError(f"max_iter must be an int >= 0, got {max_iter!r}")
     stft_kwargs = {k: v for k, v in kwargs.items() if k in _RECOGNISED}
-    P = phase_vocoder(stft(x, n_fft, **stft_kwargs), rate, phase_lock, **stft_kwargs)
+    P = phase_vocoder(stft(x, n_fft, **stft_kwargs), rate, phase_lock, lock_tol, **stft_kwargs)
     if max_iter == 0:
         return istft(P, **stft_kwargs)
     run = {"accelerated_griffin_lim": accelerated_griffin_lim, "griffin_lim": griffin_lim, "ADMM": ADMM}[method]
@@ -174,13 +237,13 @@ def shift_rate(sample_rate, n_steps, bins_per_octave=12):
 
 
 def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_iter=32, method="accelerated_griffin_lim",
-                lowpass_filter_width=6, rolloff=0.99, phase_lock=None, **kwargs):
+                lowpass_filter_width=6, rolloff=0.99, phase_lock=None, lock_tol=1e-6, **kwargs):
     r"""A waveform (L,) / (B, L) sampled at `sample_rate` raised by `n_steps` steps of `bins_per_octave` to the octave (a real
     number: fractional and negative steps are valid) at the same duration: a waveform of the same shape.
 
     It is exactly, with (rate, orig) = shift_rate(sample_rate, n_steps, bins_per_octave),
 
-        y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, phase_lock=phase_lock, **kwargs)
+        y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, phase_lock=phase_lock, lock_tol=lock_tol, **kwargs)
         if orig != sample_rate:
             y = resample(y, orig, sample_rate, lowpass_filter_width, rolloff)
 
@@ -190,7 +253,8 @@ def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_ite
     from .resample import resample
     rate, orig = shift_rate(sample_rate, n_steps, bins_per_octave)
     _checked_lock(phase_lock)
-    y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, phase_lock=phase_lock, **kwargs)
+    lock_tol = _checked_lock_tol(lock_tol)
+    y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, phase_lock=phase_lock, lock_tol=lock_tol, **kwargs)
     if orig != sample_rate:
         y = resample(y, orig, sample_rate, lowpass_filter_width, rolloff)
     n = x.shape[-1]

@@ -55,7 +55,7 @@ import torch
 from . import _lib
 from ._ingest import ingest
 from .plan import require_gpu
-from .timescale import _METHODS, _checked_rate
+from .timescale import _METHODS, _checked_lock_tol, _checked_rate
 
 __all__ = ["wsola", "ola", "time_stretch_hpss", "wsola_frames", "wsola_centres"]
 
@@ -180,16 +180,16 @@ def ola(x, rate, frame_length=256, hop_length=None, window=None, length=None):
 
 
 def time_stretch_hpss(x, rate, n_fft=None, kernel_size=31, power=2.0, hpss_iter=0, perc_frame=256, perc_hop=None, max_iter=32,
-                      method="accelerated_griffin_lim", **kwargs):
+                      method="accelerated_griffin_lim", phase_lock="identity", lock_tol=1e-6, **kwargs):
     r"""A waveform (L,) / (B, L) played `rate` times as fast with its transients kept (Driedger, Mueller & Ewert 2014): the
     harmonic part by the phase-locked vocoder, the percussive part by overlap-add with short frames.  It is exactly
 
         x_h, x_p = hpss_audio(x, n_fft, kernel_size, power, 1.0, hpss_iter, **kwargs)
-        y_h = time_stretch(x_h, rate, n_fft, max_iter, method, phase_lock="identity", **kwargs)
+        y_h = time_stretch(x_h, rate, n_fft, max_iter, method, phase_lock=phase_lock, lock_tol=lock_tol, **kwargs)
         y_p = ola(x_p, rate, perc_frame, perc_hop, length=y_h.shape[-1])
         return y_h + y_p
 
-    and has `time_stretch`'s length.  `hpss_iter` is `hpss_audio`'s `max_iter` (MISI iterations that make x_h + x_p = x);
+    with `phase_lock` "identity" (the default) or "pghi" - the harmonic branch is always locked, `None` is a ValueError - and has `time_stretch`'s length.  `hpss_iter` is `hpss_audio`'s `max_iter` (MISI iterations that make x_h + x_p = x);
     `perc_frame` / `perc_hop` are `ola`'s frame and hop.  `**kwargs` holds the STFT arguments and whatever else `time_stretch`'s
     method takes.  Both branches map output time s to input time s * rate from 0, which holds for centred frames only:
     `center=False` is a ValueError.
@@ -208,11 +208,13 @@ def time_stretch_hpss(x, rate, n_fft=None, kernel_size=31, power=2.0, hpss_iter=
     _checked_frame(perc_frame, perc_hop, "perc_frame", "perc_hop")
     if not kwargs.get("center", True):
         raise ValueError("time_stretch_hpss needs centred frames: with center=False the vocoder's output time 0 is not the input's")
-    if "phase_lock" in kwargs:
-        raise ValueError("time_stretch_hpss locks the phase itself (phase_lock='identity')")
+    if not (isinstance(phase_lock, str) and phase_lock in ("identity", "pghi")):
+        raise ValueError(f"time_stretch_hpss locks the phase of its harmonic branch: phase_lock must be 'identity' or 'pghi', "
+                         f"got {phase_lock!r}")
+    lock_tol = _checked_lock_tol(lock_tol)
     if torch.is_grad_enabled() and x.requires_grad:
         raise NotImplementedError("time_stretch_hpss is not differentiable; detach the input")
     x_h, x_p = hpss_audio(x, n_fft, kernel_size, power, 1.0, hpss_iter, **kwargs)
-    y_h = time_stretch(x_h, rate, n_fft, max_iter, method, phase_lock="identity", **kwargs)
+    y_h = time_stretch(x_h, rate, n_fft, max_iter, method, phase_lock=phase_lock, lock_tol=lock_tol, **kwargs)
     y_p = ola(x_p, rate, perc_frame, perc_hop, length=y_h.shape[-1])
     return y_h + y_p
