@@ -419,6 +419,42 @@ __device__ __forceinline__ v2f unit(float turns_times_2) {  // exp(-i*pi*x)
   return v2f{c, -s};
 }
 
+// The window table of a workgroup (M pairs of window elements in LDS), filled in two steps: win_request asks for a thread's share in
+// 16-byte loads issued back to back, win_store writes it once the values are there - the kernel builds its twiddle table in
+// between, so that one memory round trip is paid and hidden instead of one per trip of a load-and-store loop.  `wins` (nullptr: none)
+// receives the elements times `scale`, the products the loop formed (wv * scale per pair).  Workgroups of 256 threads or more.
+template <int M>
+struct WinRegs {
+  static constexpr int TRIPS = M / 2 > 256 ? M / 2 / 256 : 1;
+  v4f v[TRIPS];
+};
+template <int M>
+__device__ __forceinline__ void win_request(const float* __restrict__ window, WinRegs<M>& r) {
+  const v4f* w4 = reinterpret_cast<const v4f*>(window);
+#pragma unroll
+  for (int u = 0; u < WinRegs<M>::TRIPS; ++u) {
+    const int i = threadIdx.x + u * blockDim.x;
+    r.v[u] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    if (i < M / 2) r.v[u] = w4[i];
+  }
+}
+template <int M>
+__device__ __forceinline__ void win_store(const WinRegs<M>& r, v2f* lds_win, v2f* lds_wins = nullptr, float scale = 1.0f) {
+#pragma unroll
+  for (int u = 0; u < WinRegs<M>::TRIPS; ++u) {
+    const int i = threadIdx.x + u * blockDim.x;
+    if (i < M / 2) {
+      const v2f lo = v2f{r.v[u].x, r.v[u].y}, hi = v2f{r.v[u].z, r.v[u].w};
+      lds_win[2 * i] = lo;
+      lds_win[2 * i + 1] = hi;
+      if (lds_wins != nullptr) {
+        lds_wins[2 * i] = lo * scale;
+        lds_wins[2 * i + 1] = hi * scale;
+      }
+    }
+  }
+}
+
 template <int R>
 __device__ __forceinline__ LaneConst<R> lane_consts() {
   using G = Geo<R>;
@@ -896,7 +932,8 @@ __device__ __forceinline__ void st_stream(v4f* p, v4f v) {
 // the first were stored as two partial sums (the chunk's own frames in x, the previous chunk's last three
 // frames in `xtail`); they are added here.  Edge (reflected) blocks never touch such blocks because the
 // first and the last chunk are at least 6 frames long.
-template <int R>
+// NT: the interior rows with non-temporal loads (a signal one wave reads once a launch: z_t in fused_td_body).
+template <int R, bool NT = false>
 __device__ __forceinline__ void load_block4(const float* __restrict__ xrow, const float* __restrict__ tailrow,
                                            long long L, int T, int c, int t_begin, int t_end, int j, int lane,
                                            int pad_mode, v2f (&q)[R / 4]) {
@@ -905,7 +942,10 @@ __device__ __forceinline__ void load_block4(const float* __restrict__ xrow, cons
   if (j >= 2 && j <= T) {
     const v2f* src = reinterpret_cast<const v2f*>(xrow + s0);   // uniform
 #pragma unroll
-    for (int i = 0; i < R / 4; ++i) q[i] = src[64u * i + (unsigned)lane];
+    for (int i = 0; i < R / 4; ++i) {
+      const v2f* p = &src[64u * i + (unsigned)lane];
+      q[i] = NT ? __builtin_nontemporal_load(p) : *p;
+    }
     // a wave only ever reads blocks t_begin .. t_end + 2 of its own chunk c: split blocks are the chunk's
     // own first three (other half from chunk c-1) and the next chunk's first three (other half: this chunk's)
     int tc = -1, off = 0;

@@ -19,6 +19,7 @@ struct FastState {
   bool plain_state = false;
   int n_partials = 0;
   int nchunks = 0, skew = 0, OV = 0;
+  int max_partials() const { return 0; }
   T* state_rows() const { return nullptr; }
   const T* state_tails() const { return nullptr; }
   int setup(const specinv_stft_cfg&, const std::vector<T>&, int64_t, int) { return SPECINV_OK; }
@@ -315,7 +316,7 @@ struct FastState<float> {
     }
     a.window = pl.window.template as<float>();
     a.env = pl.env.template as<float>();
-    a.partials = pl.partials.template as<double>();
+    a.partials = pl.partials_out();
     a.T = pl.Tn();
     a.nchunks = nchunks;
     a.skew = skew;
@@ -754,6 +755,10 @@ struct FastState<float> {
     return SPECINV_OK;
   }
 
+  // the most pairs of partial sums an evaluating launch of this plan leaves (n_partials after it): what a slab of a run with
+  // deferred read-back holds
+  int max_partials() const { return semi ? n_waves : n_waves * fast::kEvalPieces; }
+
   template <typename P>
   int iterate_semi(P& pl, int n_iter, bool eval_last) {
     SI_TRY(pl.partials.reserve(std::max<size_t>((size_t)n_waves * 2, 3 * 1024) * sizeof(double)));
@@ -834,22 +839,28 @@ struct FastState<float> {
 
   template <typename P>
   int get_wave(P& pl, float* out) {
-    SI_HIP(hipMemcpyAsync(out, xb[cur].p, (size_t)pl.B() * pl.length * sizeof(float), hipMemcpyDeviceToDevice, pl.stream));
-    if (!semi && nchunks > 1) {
-      const int hop = pl.cfg.hop_length;
-      const long long total = (long long)pl.B() * nchunks * (OV - 1) * hop;
-      const void* fn = nullptr;
-      SPECINV_R_SWITCH(R, if constexpr (RR % 8 == 0) { if (OV == 8) fn = (const void*)fast::k_add_tails<RR, 8>; }
-                       if (OV == 4) fn = (const void*)fast::k_add_tails<RR, 4>;
-                       if (OV == 2) fn = (const void*)fast::k_add_tails<RR, 2>);
-      float* xo = out;
-      const float* tl = xtail[cur].template as<float>();
-      int Tn = pl.Tn(), nc = nchunks;
-      long long Ln = (long long)pl.length, tot = total;
-      int sk = skew;
-      void* kargs[] = {&xo, &tl, &Tn, &nc, &Ln, &tot, &sk};
-      SI_HIP(hipLaunchKernel(fn, dim3((unsigned)ceil_div(total, 256)), dim3(256), kargs, 0, pl.stream));
+    if (semi || nchunks <= 1) {      // the rows are whole
+      SI_HIP(hipMemcpyAsync(out, xb[cur].p, (size_t)pl.B() * pl.length * sizeof(float), hipMemcpyDeviceToDevice, pl.stream));
+      return SPECINV_OK;
     }
+    // the rows and the chunk tails beside them, added on the way out (k_wave_out)
+    const bool wide = pl.length % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const void* fn = nullptr;
+    SPECINV_R_SWITCH(R, if constexpr (RR % 8 == 0) {
+                       if (OV == 8) fn = wide ? (const void*)fast::k_wave_out<RR, 8, v4f> : (const void*)fast::k_wave_out<RR, 8, float>;
+                     }
+                     if (OV == 4) fn = wide ? (const void*)fast::k_wave_out<RR, 4, v4f> : (const void*)fast::k_wave_out<RR, 4, float>;
+                     if (OV == 2) fn = wide ? (const void*)fast::k_wave_out<RR, 2, v4f> : (const void*)fast::k_wave_out<RR, 2, float>);
+    SI_CHECK(fn != nullptr, SPECINV_EUNSUPPORTED, "no fused kernel for n_fft / hop = %d", OV);
+    float* xo = out;
+    const float* xi = xb[cur].template as<float>();
+    const float* tl = xtail[cur].template as<float>();
+    int Tn = pl.Tn(), nc = nchunks, sk = skew;
+    long long Ln = (long long)pl.length;
+    int nblk = (int)ceil_div(Ln, (long long)pl.cfg.hop_length);
+    long long tot = (long long)pl.B() * nblk;
+    void* kargs[] = {&xo, &xi, &tl, &Tn, &nc, &Ln, &nblk, &tot, &sk};
+    SI_HIP(hipLaunchKernel(fn, dim3((unsigned)ceil_div(tot, 4LL * fast::kWaveOutBlocks)), dim3(256), kargs, 0, pl.stream));
     return SPECINV_OK;
   }
 

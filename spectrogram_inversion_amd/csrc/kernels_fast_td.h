@@ -30,11 +30,11 @@ __device__ __forceinline__ const auto& td_pick(const A& a, const B& b) {
 
 
 // one hop-block of the sample window (the tuned n_fft/4 copy of the loader where it applies)
-template <int R, int OV>
+template <int R, int OV, bool NT = false>
 __device__ __forceinline__ void td_load_block(const float* __restrict__ xrow, const float* __restrict__ tailrow, long long L,
                                               int T, int c, int t_begin, int t_end, int j, int lane, int pad_mode,
                                               v2f (&q)[R / OV]) {
-  if constexpr (OV == 4) load_block4<R>(xrow, tailrow, L, T, c, t_begin, t_end, j, lane, pad_mode, q);
+  if constexpr (OV == 4) load_block4<R, NT>(xrow, tailrow, L, T, c, t_begin, t_end, j, lane, pad_mode, q);
   else load_block<R, OV>(xrow, tailrow, L, T, c, t_begin, t_end, j, lane, pad_mode, q);
 }
 
@@ -157,6 +157,27 @@ __device__ __forceinline__ void td_fft_inverse(v2f (&z)[R], const LaneConst<R>& 
   }
 }
 
+// Lane 0 of the conjugate-partner exchange is its own partner: after the shuffle it takes eight values of its own.  Written as
+// eight 64-bit moves under exec = 1 (saved and restored around them) instead of sixteen selects on a lane mask; the values are the
+// same.  Only called in uniform control flow with all lanes active.
+__device__ __forceinline__ void td_lane0_mov8(v2f& d0, v2f& d1, v2f& d2, v2f& d3, v2f& d4, v2f& d5, v2f& d6, v2f& d7, v2f s0, v2f s1,
+                                              v2f s2, v2f s3, v2f s4, v2f s5, v2f s6, v2f s7) {
+  unsigned long long saved;
+  asm("s_mov_b64 %8, exec\n\t"
+      "s_mov_b64 exec, 1\n\t"
+      "v_mov_b64 %0, %9\n\t"
+      "v_mov_b64 %1, %10\n\t"
+      "v_mov_b64 %2, %11\n\t"
+      "v_mov_b64 %3, %12\n\t"
+      "v_mov_b64 %4, %13\n\t"
+      "v_mov_b64 %5, %14\n\t"
+      "v_mov_b64 %6, %15\n\t"
+      "v_mov_b64 %7, %16\n\t"
+      "s_mov_b64 exec, %8"
+      : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(d4), "+v"(d5), "+v"(d6), "+v"(d7), "=&s"(saved)
+      : "v"(s0), "v"(s1), "v"(s2), "v"(s3), "v"(s4), "v"(s5), "v"(s6), "v"(s7));
+}
+
 template <int R, int OV, bool EARLY, bool EVAL>
 __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   using G = Geo<R>;
@@ -172,15 +193,13 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   v2f* tr = lds_tw1 + (R - 1) * 64 + wib * G::TR;
 
-  for (int i = threadIdx.x; i < M; i += blockDim.x) {
-    const v2f wv = v2f{a.window[2 * i], a.window[2 * i + 1]};
-    lds_win[i] = wv;
-    lds_wins[i] = wv * a.inv_scale;
-  }
+  WinRegs<M> wreg;
+  win_request<M>(a.window, wreg);      // (in flight while the twiddles are built)
   for (int i = threadIdx.x; i < (R - 1) * 64; i += blockDim.x) {
     const int k1 = i / 64 + 1, l = i & 63;
     lds_tw1[i] = unit(2.0f * (float)((l * k1) % M) / (float)M);   // W_M^(l*k1)
   }
+  win_store<M>(wreg, lds_win, lds_wins, a.inv_scale);
   __syncthreads();
 
   int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);   // (scalar: the frame loop and its padding tests branch on the scalar unit; left to the compiler the work-group size may arrive in a vector register and make all of it per-lane)
@@ -249,8 +268,8 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
   v2f xq[NB][QU], xn[QU];
 #pragma unroll
   for (int q = 0; q < NB; ++q)
-    td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t_begin + q, lane, a.pad_mode, xq[q]);
-  td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t_begin + NB, lane, a.pad_mode, xn);
+    td_load_block<R, OV, true>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t_begin + q, lane, a.pad_mode, xq[q]);
+  td_load_block<R, OV, true>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t_begin + NB, lane, a.pad_mode, xn);
 
   // The overlap-add envelope is periodic in the hop wherever all n_fft / hop frames that cover a sample exist (hop-blocks NB .. T-1:
   // the same summands in the same order, plan_impl.h): one block of its reciprocal is kept in registers instead of being loaded for
@@ -363,7 +382,7 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     // (the block after a chunk's last frame has no reader: the empty asm defines xn there, so that the compiler does not carry
     // the old block round the loader's arms in a second set of registers)
     if (t + 1 < t_end) {
-      td_load_block<R, OV>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
+      td_load_block<R, OV, true>(zrow, tailrow, a.L, a.T, c, t_begin, t_end, t + OV, lane, a.pad_mode, xn);
     } else {
 #pragma unroll
       for (int i = 0; i < QU; ++i) asm volatile("" : "=v"(xn[i]));
@@ -373,11 +392,18 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
     td_fft_forward<R>(z, k, twr, tr, tsc);
 
     v2f rc[H];
+    if constexpr (R == 16) {
 #pragma unroll
-    for (int m = H; m < R; ++m) {
-      const v2f got = shfl2(z[m], k.partner);
-      const v2f own = z[(m + 1) % R];              // lane 0 is its own partner, shifted by one register
-      rc[m - H] = v2f{lane == 0 ? own.x : got.x, lane == 0 ? own.y : got.y};
+      for (int m = H; m < R; ++m) rc[m - H] = shfl2(z[m], k.partner);
+      // lane 0 is its own partner, shifted by one register
+      td_lane0_mov8(rc[0], rc[1], rc[2], rc[3], rc[4], rc[5], rc[6], rc[7], z[9], z[10], z[11], z[12], z[13], z[14], z[15], z[0]);
+    } else {
+#pragma unroll
+      for (int m = H; m < R; ++m) {
+        const v2f got = shfl2(z[m], k.partner);
+        const v2f own = z[(m + 1) % R];              // lane 0 is its own partner, shifted by one register
+        rc[m - H] = v2f{lane == 0 ? own.x : got.x, lane == 0 ? own.y : got.y};
+      }
     }
 
     // ---- per pair: split -> (+ c0 term) -> projection -> fold back
@@ -439,11 +465,18 @@ __device__ __forceinline__ void fused_td_body(const FastArgs& a) {
       const v2f am = (smid * mmid) * ref_rcp_abs(ref_norm2(smid));
       zmid = am * v2f{2.0f, -2.0f};
     }
+    if constexpr (R == 16) {
 #pragma unroll
-    for (int m = H; m < R; ++m) {
-      const v2f got = shfl2(back[R - 1 - m], k.partner);
-      const v2f l0 = (m == H) ? zmid : back[(R - m) % H];
-      z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
+      for (int m = H; m < R; ++m) z[m] = shfl2(back[R - 1 - m], k.partner);
+      td_lane0_mov8(z[8], z[9], z[10], z[11], z[12], z[13], z[14], z[15], zmid, back[7], back[6], back[5], back[4], back[3], back[2],
+                    back[1]);
+    } else {
+#pragma unroll
+      for (int m = H; m < R; ++m) {
+        const v2f got = shfl2(back[R - 1 - m], k.partner);
+        const v2f l0 = (m == H) ? zmid : back[(R - m) % H];
+        z[m] = v2f{lane == 0 ? l0.x : got.x, lane == 0 ? l0.y : got.y};
+      }
     }
 
     td_fft_inverse<R>(z, k, twr, tr, tsc);
@@ -557,11 +590,13 @@ __global__ __launch_bounds__(256, kEvalWaves) void k_eval_td(FastArgs a) {
   v2f* lds_tw1 = lds_win + M;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   v2f* tr = lds_tw1 + (R - 1) * 64 + wib * G::TR;
-  for (int i = threadIdx.x; i < M; i += blockDim.x) lds_win[i] = v2f{a.window[2 * i], a.window[2 * i + 1]};
+  WinRegs<M> wreg;
+  win_request<M>(a.window, wreg);      // (in flight while the twiddles are built)
   for (int i = threadIdx.x; i < (R - 1) * 64; i += blockDim.x) {
     const int k1 = i / 64 + 1, l = i & 63;
     lds_tw1[i] = unit(2.0f * (float)((l * k1) % M) / (float)M);
   }
+  win_store<M>(wreg, lds_win);
   __syncthreads();
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wib);
   if (w >= a.n_waves * kEvalSub) return;

@@ -480,11 +480,13 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
   v2f* lds_tw1 = lds_win + M;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   v2f* tr = lds_tw1 + (R - 1) * 64 + wib * G::TR;
-  for (int i = threadIdx.x; i < M; i += blockDim.x) lds_win[i] = v2f{a.window[2 * i], a.window[2 * i + 1]};
+  WinRegs<M> wreg;
+  win_request<M>(a.window, wreg);      // (in flight while the twiddles are built)
   for (int i = threadIdx.x; i < (R - 1) * 64; i += blockDim.x) {
     const int k1 = i / 64 + 1, l = i & 63;
     lds_tw1[i] = unit(2.0f * (float)((l * k1) % M) / (float)M);
   }
+  win_store<M>(wreg, lds_win);
   __syncthreads();
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + wib);   // (scalar: the frame loop and its padding tests branch on the scalar unit; left to the compiler the work-group size may arrive in a vector register and make all of it per-lane)
   if (w >= a.n_waves) return;
@@ -504,18 +506,32 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
   v2f acc[NB * QU];
 #pragma unroll
   for (int i = 0; i < NB * QU; ++i) acc[i] = v2f{0.0f, 0.0f};
+  // A frame's spectrum (H records of 16 bytes per lane, lane 0's middle bin) and the envelope block its output needs are
+  // requested a frame ahead, once the projection has read the registers: in flight during the inverse transform, not waited for
+  // at the top of the frame.  Nothing is requested past the chunk's last frame.
+  v4f pp[H];
+  v2f pmid = v2f{0.0f, 0.0f};
+  v2f envb[QU];
+#pragma unroll
+  for (int i = 0; i < QU; ++i) envb[i] = v2f{1.0f, 1.0f};     // (halo frames write nothing and request none)
+#define SPECINV_ISTFT_LOADS(TT)                                                            \
+  do {                                                                                     \
+    const int tt_ = (TT);                                                                  \
+    const long long fl_ = (long long)b * a.T + tt_;                                        \
+    const v4f* pin_ = a.P_in + fl_ * (H * 64);                                             \
+    _Pragma("unroll") for (int j = 0; j < H; ++j) pp[j] = pin_[j * 64u + ulane];         \
+    if (lane == 0) pmid = a.Pmid_in[fl_];                                                  \
+    if (tt_ >= t_begin && tt_ >= PB) {                                                     \
+      const v2f* envp_ = reinterpret_cast<const v2f*>(a.env + (long long)(tt_ - PB) * HOP); \
+      _Pragma("unroll") for (int i = 0; i < QU; ++i) envb[i] = envp_[64u * i + ulane];     \
+    }                                                                                      \
+  } while (0)
+  SPECINV_ISTFT_LOADS(t_start);
   for (int t = t_start; t < t_end; ++t) {
     asm volatile("" ::: "memory");
     v2f wn = k.wn;
     asm volatile("" : "+v"(wn));
     const bool live = t >= t_begin;
-    const long long fi = (long long)b * a.T + t;
-    const v4f* pin = a.P_in + fi * (H * 64);
-    v4f pp[H];
-#pragma unroll
-    for (int j = 0; j < H; ++j) pp[j] = pin[j * 64u + ulane];
-    v2f pmid = v2f{0.0f, 0.0f};
-    if (lane == 0) pmid = a.Pmid_in[fi];
     v2f z[R], back[H];
 #pragma unroll
     for (int j = 0; j < H; ++j) {
@@ -531,6 +547,10 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
       back[j] = conj_sub_i(e2i, o2i);
     }
     const v2f zmid = pmid * v2f{2.0f * a.inv_scale, -2.0f * a.inv_scale};
+    v2f envc[QU];      // (this frame's envelope block: its registers take the next frame's below)
+#pragma unroll
+    for (int i = 0; i < QU; ++i) envc[i] = envb[i];
+    if (t + 1 < t_end) SPECINV_ISTFT_LOADS(t + 1);
 #pragma unroll
     for (int m = H; m < R; ++m) {
       const v2f got = shfl2(back[R - 1 - m], k.partner);
@@ -541,11 +561,9 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
 #pragma unroll
     for (int u = 0; u < R; ++u) z[u] = z[u] * lds_win[64 * u + lane];
     if (live && t >= PB) {
-      const long long o0 = (long long)(t - PB) * HOP;
-      const v2f* envp = reinterpret_cast<const v2f*>(a.env + o0);
-      v2f* outp = reinterpret_cast<v2f*>(orow + o0);
+      v2f* outp = reinterpret_cast<v2f*>(orow + (long long)(t - PB) * HOP);
 #pragma unroll
-      for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[i] + z[i], envp[64u * i + ulane]);
+      for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[i] + z[i], envc[i]);
     }
 #pragma unroll
     for (int i = 0; i < QU; ++i) {
@@ -564,6 +582,7 @@ __global__ __launch_bounds__(256, R >= 32 ? 1 : kMinWaves) void k_fused_istft(Fa
       for (int i = 0; i < QU; ++i) outp[64u * i + ulane] = env_apply(acc[q * QU + i], envp[64u * i + ulane]);
     }
   }
+#undef SPECINV_ISTFT_LOADS
 }
 
 

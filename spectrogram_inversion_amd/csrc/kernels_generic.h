@@ -915,6 +915,20 @@ static __global__ void k_finish_partials(const double* __restrict__ partials, in
   }
 }
 
+// The same for gridDim.x sets of partials `stride` doubles apart, a workgroup each: sums[n_comp * s + k] of slab s is the value
+// k_finish_partials gives for it (the same 256 strided sums, the same block_sum).
+static __global__ void k_finish_slabs(const double* __restrict__ slabs, int64_t stride, int64_t n, int n_comp,
+                                      double* __restrict__ sums) {
+  __shared__ double red[16];
+  const double* partials = slabs + (int64_t)blockIdx.x * stride;
+  for (int k = 0; k < n_comp; ++k) {
+    double v = 0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) v += partials[n_comp * i + k];
+    const double tot = block_sum(v, red);
+    if (threadIdx.x == 0) sums[n_comp * blockIdx.x + k] = tot;
+  }
+}
+
 static __global__ void k_store2(double* __restrict__ out, double a, double b) {
   out[0] = a;
   out[1] = b;

@@ -173,22 +173,46 @@ __global__ __launch_bounds__(1024) void k_phase_init_pairs(const float* __restri
   if (threadIdx.x == 0) partials[blockIdx.x] = tot;
 }
 
-// x += the tail partial sums (final waveform for get_wave)
-template <int R, int OV>
-__global__ void k_add_tails(float* __restrict__ x, const float* __restrict__ xtail, int T, int nchunks, long long L,
-                            long long total, int skew) {
-  constexpr int HOP = Ovl<R, OV>::HOP, NB = Ovl<R, OV>::NB, PB = Ovl<R, OV>::PB;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, c, q, sample) over tails
-  if (i >= total) return;
-  const int smp = i % HOP;
-  const int q = (i / HOP) % NB;
-  const int c = (i / (NB * HOP)) % nchunks;
-  const long long b = i / ((long long)NB * HOP * nchunks);
-  if (c >= nchunks - 1) return;                       // the last chunk has no successor
-  const int blk = chunk_begin(c + 1, T, nchunks, skew) + q; // padded-signal hop-block
-  // register layout of a block: element (reg i2, lane l, comp e) <-> sample 128*i2 + 2*l + e
-  const int i2 = smp / 128, rem = smp % 128;
-  x[b * L + (long long)(blk - PB) * HOP + smp] += xtail[((b * nchunks + c) * NB + q) * HOP + (i2 * 64 + rem / 2) * 2 + (rem & 1)];
+// out = x + the tail partial sums (the final waveform for get_wave) in one pass.  The first NB hop-blocks of every chunk but the
+// first hold two partial sums - the chunk's own frames in x, the previous chunk's last NB frames in xtail, stored in sample order
+// (register i, lane l, component e <-> sample 128 i + 2 l + e) - every other block is copied.  x and xtail stay as they are.
+// A wave takes kWaveOutBlocks consecutive hop-blocks of the (item, hop-block) space, so that which chunk a block belongs to is
+// found once per block on the scalar unit.  Vec: float4 where L and `out` allow 16-byte accesses, else float.
+constexpr int kWaveOutBlocks = 4;
+template <int R, int OV, typename Vec>
+__global__ __launch_bounds__(256) void k_wave_out(float* __restrict__ out, const float* __restrict__ x,
+                                                  const float* __restrict__ xtail, int T, int nchunks, long long L, int nblk,
+                                                  long long total, int skew) {
+  constexpr int HOP = Ovl<R, OV>::HOP, NB = Ovl<R, OV>::NB, PB = Ovl<R, OV>::PB, V = (int)(sizeof(Vec) / sizeof(float));
+  static_assert(HOP % 4 == 0, "a hop-block is whole 16-byte groups");
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long long first = ((long long)blockIdx.x * 4 + wave) * kWaveOutBlocks;
+  for (int u = 0; u < kWaveOutBlocks; ++u) {
+    const long long g = first + u;                     // (item, hop-block of the signal)
+    if (g >= total) break;
+    const long long b = g / nblk;
+    const int hb = (int)(g - b * nblk);
+    const int blk = hb + PB;                           // ... of the padded signal, which chunk_begin counts
+    // the last chunk that begins at or before blk (chunk_begin rises with c; a chunk is longer than NB frames)
+    int lo = 0, hi = nchunks - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (chunk_begin(mid, T, nchunks, skew) <= blk) lo = mid;
+      else hi = mid - 1;
+    }
+    const int q = blk - chunk_begin(lo, T, nchunks, skew);
+    const bool seam = lo >= 1 && q < NB;
+    const long long o0 = (long long)hb * HOP;
+    const float* xs = x + b * L + o0;
+    float* os = out + b * L + o0;
+    const float* ts = seam ? xtail + ((b * nchunks + (lo - 1)) * NB + q) * HOP : xs;
+    const int n = (int)(L - o0 < HOP ? L - o0 : HOP);  // the last block of an item may be short
+    for (int s = lane * V; s < n; s += 64 * V) {
+      Vec v = *reinterpret_cast<const Vec*>(xs + s);
+      if (seam) v += *reinterpret_cast<const Vec*>(ts + s);
+      *reinterpret_cast<Vec*>(os + s) = v;
+    }
+  }
 }
 
 // ---- layout conversion between the frame-major (B*T, F) spectra and the pair layout ---------------

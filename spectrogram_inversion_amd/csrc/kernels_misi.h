@@ -18,7 +18,7 @@ struct MisiMixArgs {
   const T* mix;     // (n_mix, L)
   // The float32 fused kernels keep a signal as x plus chunk tails: the first nb hop-blocks of every chunk but the first are two
   // partial sums, the chunk's own frames in x and the previous chunk's last frames in tail[row][c][q][hop] (fast_core.h:
-  // load_block adds them on load, kernels_layout.h: k_add_tails for get_wave).  The sum over the sources is that of the whole
+  // load_block adds them on load, kernels_layout.h: k_wave_out for get_wave).  The sum over the sources is that of the whole
   // waveforms, the correction goes to x alone: x + e + tail is what the next launch loads.  nullptr: x is the whole waveform.
   const T* tail;
   int64_t L;

@@ -72,6 +72,13 @@ struct PlanT final : PlanBase {
   RtisiStream<T> rstream;
   DevBuf lb_scal, lb_part;              // device scalars / partial sums of the L-BFGS passes
   DevBuf eval_log;                      // per-evaluation sums of a run with deferred read-back
+  // ... whose evaluating launches on the float32 wave-level kernels each leave their partial sums in a slab of their own (slot x
+  // slab_stride doubles), finished by one launch in read_deferred
+  DevBuf eval_slabs;
+  int64_t slab_stride = 0, slab_parts = 0;   // doubles per slab; pairs of partial sums the run's evaluations leave in one
+  int slab_slots = 0;                        // slabs reserved by begin_deferred (0: one finishing launch per evaluation)
+  double* eval_partials = nullptr;           // where the next evaluating launch writes (nullptr: `partials`)
+  double* partials_out() const { return eval_partials != nullptr ? eval_partials : partials.as<double>(); }
   DevBuf tf_mel, tf_mel_tiled, tf_mel_tiled_t, tf_spec, tf_v;   // transform (L_BFGS) scratch
   DevBuf tf_mel_a, tf_mel_b, tf_obj_tab;   // non-zero filterbank blocks in MFMA operand order + block table (one-launch objective)
   int tf_obj_mt = 0;                    // its 16-row mel tiles (0: the objective runs as a kernel chain)
@@ -841,9 +848,14 @@ struct PlanT final : PlanBase {
       for (int i = 0; i < n_iter; ++i) SI_TRY(iterate(1, eval_last && i == n_iter - 1, s));
       return SPECINV_OK;
     }
+    bool slab = false;     // this call's evaluation leaves its partial sums in a slab of the deferred run
     if (fast_path()) {
       fast.keep_state = fast.two ? keep_latched : keep_state;
-      SI_TRY(fast.iterate(*this, n_iter, eval_last));
+      slab = eval_last && eval_dev_out == nullptr && deferred_slot >= 0 && deferred_slot < slab_slots;
+      eval_partials = slab ? eval_slabs.as<double>() + (int64_t)deferred_slot * slab_stride : nullptr;
+      const int rc = fast.iterate(*this, n_iter, eval_last);
+      eval_partials = nullptr;
+      SI_TRY(rc);
     } else {
       if (!(use_wave && wave_iter_ola_chunks<T>(N(), cfg.hop_length, Tn(), B(), cfg.onesided != 0) > 0)) SI_TRY(frames_needed());
       const T inv1p = T(1) / (T)(1.0 + (double)coef);
@@ -955,6 +967,14 @@ struct PlanT final : PlanBase {
         SI_HIP(hipGetLastError());
         return SPECINV_OK;
       }
+      if (slab) {
+        // deferred evaluation on the wave-level kernels: the partial sums wait in their slab for read_deferred's one launch
+        SI_CHECK(2 * n_part <= slab_stride && (slab_parts == 0 || slab_parts == n_part), SPECINV_ESTATE,
+                 "an evaluation left %lld pairs of partial sums in a slab sized for %lld", (long long)n_part,
+                 (long long)(slab_parts ? slab_parts : slab_stride / 2));
+        slab_parts = n_part;
+        return SPECINV_OK;
+      }
       if (deferred_slot >= 0) {
         // deferred evaluation (run_loop with tol == 0 and no callback): keep the sums on the device
         SI_TRY(eval_log.reserve((size_t)(deferred_slot + 1) * 2 * sizeof(double)));
@@ -980,11 +1000,27 @@ struct PlanT final : PlanBase {
 
   int begin_deferred(int n_slots) override {
     SI_TRY(eval_log.reserve((size_t)std::max(1, n_slots) * 2 * sizeof(double)));
+    slab_slots = 0;
+    slab_parts = 0;
+    if (fast_path() && n_slots > 0) {
+      slab_stride = 2 * (int64_t)fast.max_partials();
+      SI_TRY(eval_slabs.reserve((size_t)n_slots * slab_stride * sizeof(double)));
+      slab_slots = n_slots;
+    }
     return SPECINV_OK;
   }
 
   int read_deferred(int n_slots, double* out /* n_slots x 4 */) override {
     std::vector<double> h((size_t)n_slots * 2);
+    if (n_slots > 0 && slab_slots > 0) {
+      // every slab's sums in one launch: a workgroup per slot, each summing as k_finish_partials does
+      SI_CHECK(n_slots <= slab_slots && slab_parts > 0, SPECINV_ESTATE, "read_deferred: %d slots asked for, %d filled", n_slots,
+               slab_parts > 0 ? slab_slots : 0);
+      hipLaunchKernelGGL(k_finish_slabs, dim3(n_slots), dim3(256), 0, stream, eval_slabs.as<double>(), slab_stride, slab_parts, 2,
+                         eval_log.as<double>());
+      SI_HIP(hipGetLastError());
+      slab_slots = 0;
+    }
     if (n_slots > 0) {
       SI_HIP(hipMemcpyAsync(h.data(), eval_log.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     }
