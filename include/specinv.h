@@ -189,6 +189,22 @@ enum { SPECINV_HPSS_COMPONENTS = 0, SPECINV_HPSS_MASKS = 1, SPECINV_HPSS_MEDIANS
 int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames, int32_t win_harm,
                  int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode, int32_t is_complex,
                  int32_t dtype, int32_t device, void* hip_stream);
+/* Spectral envelope (not in the reference; csrc/kernels_envelope.h): the true-envelope estimator of Roebel & Rodet 2005 in one
+ * launch.  spec is a one-sided spectrogram on HIP device `device`, (batch, n_freq, n_frames) or with frame_major != 0
+ * (batch, n_frames, n_freq), real non-negative magnitudes of `dtype` or, with is_complex != 0, (re, im) pairs of `dtype`; out is real,
+ * in the same layout; amin is a (batch,) device array of `dtype`; enqueued on hip_stream (NULL: the null stream).  No plan: nothing
+ * about an STFT is read but N = 2 (n_freq - 1), and nothing is kept.  Per item and frame:
+ *     a0[k] = log(max(|spec[k]|, amin[item])), or 0 for every k where amin[item] <= 0 (an all-zero item) ;
+ *     C(a)  = Re rfft(irfft(a, N) * l),  l[q] = 1 if min(q, N - q) <= order else 0 ;
+ *     V_0 = C(a0), V_i = C(max(a0, V_{i-1})) for i = 1 ... n_iter ;  out = V_{n_iter} if out_log != 0 else exp(V_{n_iter}).
+ * n_iter is a count, not a stop rule; n_iter = 0 is plain cepstral smoothing; order = N / 2 is the identity.  Any batch: it is not
+ * a launch dimension of its own.  NaN input is unspecified.  Stateless: a running method is not disturbed.
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL pointer (spec, out, amin) ; out == spec ; batch or
+ * n_frames < 1 ; n_iter outside 0 ... 256 ; an unknown dtype ; then SPECINV_EUNSUPPORTED for SPECINV_F64 ; an n_freq that is not
+ * 129, 257, 513 or 1025 (n_fft 256, 512, 1024, 2048) ; then SPECINV_EINVAL for order outside 0 ... N / 2. */
+int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int64_t batch, int32_t n_freq, int32_t n_frames,
+                              int32_t order, int32_t n_iter, int32_t out_log, int32_t is_complex, int32_t frame_major, int32_t dtype,
+                              int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

@@ -7,6 +7,7 @@
 #include "kernels_mel_nnls.h"
 #include "kernels_mel_nnls_adjoint.h"
 #include "kernels_hpss.h"
+#include "kernels_envelope.h"
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
 #include "kernels_pghi.h"
@@ -348,6 +349,27 @@ int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int3
                               margin_harm, margin_perc, out_mode, is_complex != 0, stream);
   return hpss_launch<double>((const double*)spec, (double*)out_a, (double*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
                              margin_harm, margin_perc, out_mode, is_complex != 0, stream);
+}
+int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int64_t batch, int32_t n_freq, int32_t n_frames,
+                              int32_t order, int32_t n_iter, int32_t out_log, int32_t is_complex, int32_t frame_major, int32_t dtype,
+                              int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec && out && amin, SPECINV_EINVAL, "specinv_spectral_envelope: NULL %s", !spec ? "spec" : !out ? "out" : "amin");
+  SI_CHECK(out != spec, SPECINV_EINVAL, "specinv_spectral_envelope: out must not alias spec");
+  SI_CHECK(batch >= 1 && n_frames >= 1, SPECINV_EINVAL, "specinv_spectral_envelope: batch and n_frames must be >= 1, got %lld and %d",
+           (long long)batch, n_frames);
+  SI_CHECK(n_iter >= 0 && n_iter <= kEnvMaxIter, SPECINV_EINVAL, "specinv_spectral_envelope: n_iter must be in 0 ... %d, got %d",
+           kEnvMaxIter, n_iter);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_spectral_envelope: float32 only");
+  SI_CHECK(n_freq == 129 || n_freq == 257 || n_freq == 513 || n_freq == 1025, SPECINV_EUNSUPPORTED,
+           "specinv_spectral_envelope: n_freq must be 129, 257, 513 or 1025 (n_fft 256, 512, 1024 or 2048), got %d", n_freq);
+  SI_CHECK(order >= 0 && order <= n_freq - 1, SPECINV_EINVAL, "specinv_spectral_envelope: order must be in 0 ... %d, got %d",
+           n_freq - 1, order);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  return envelope_launch((const float*)spec, (float*)out, (const float*)amin, batch, n_freq, n_frames, order, n_iter, out_log != 0,
+                         is_complex != 0, frame_major != 0, static_cast<hipStream_t>(hip_stream));
 }
 int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
                   int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,

@@ -25,6 +25,7 @@ done right" (Prusa & Holighaus 2017), which also helps on noisy and transient in
 2^(-n_steps / bins_per_octave), then `resample` (resample.py) back to the original rate and length.
 
     z = si.pitch_shift(x, 22050, 4, n_fft=1024, hop_length=256, window=w)              # four semitones up, as long as x
+    z = si.pitch_shift(x, 22050, 4, n_fft=1024, hop_length=256, window=w, preserve_formants=True)   # ... with x's formants (envelope.py)
 
 Not part of the reference's surface.
 """
@@ -237,7 +238,8 @@ def shift_rate(sample_rate, n_steps, bins_per_octave=12):
 
 
 def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_iter=32, method="accelerated_griffin_lim",
-                lowpass_filter_width=6, rolloff=0.99, phase_lock=None, lock_tol=1e-6, **kwargs):
+                lowpass_filter_width=6, rolloff=0.99, phase_lock=None, lock_tol=1e-6, preserve_formants=False, formant_order=None,
+                formant_iter=16, **kwargs):
     r"""A waveform (L,) / (B, L) sampled at `sample_rate` raised by `n_steps` steps of `bins_per_octave` to the octave (a real
     number: fractional and negative steps are valid) at the same duration: a waveform of the same shape.
 
@@ -249,15 +251,33 @@ def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_ite
 
     and then y[..., :L], zero-padded on the right to L where it is shorter - torchaudio's definition, its phase vocoder refined by
     `method`.  `**kwargs` are `time_stretch`'s; dtype and device rules are `time_stretch`'s and `resample`'s.
+
+    That moves the formants with the pitch: a voice raised by four steps is a smaller head.  With `preserve_formants=True` the
+    result z of the above keeps the spectral envelope of `x`; it is exactly
+
+        impose_envelope(z, x, n_fft, formant_order or default_envelope_order(sample_rate), formant_iter, **stft_kwargs)
+
+    (envelope.py) with the STFT arguments among `**kwargs`: `formant_order` is the cepstral order of the envelope (an int in
+    0 ... n_fft / 2; None or 0: the default for the sampling rate) and `formant_iter` the number of true-envelope passes
+    (0 ... 256).  It costs two more STFTs, two envelopes and an inverse STFT, and `spectral_envelope`'s limits apply (float32,
+    n_fft 256 ... 2048, one-sided).  With the default `False` nothing changes.
     """
+    from .envelope import _checked_iter, _checked_order, default_envelope_order, impose_envelope
     from .resample import resample
     rate, orig = shift_rate(sample_rate, n_steps, bins_per_octave)
     _checked_lock(phase_lock)
     lock_tol = _checked_lock_tol(lock_tol)
+    if formant_order is not None:
+        w = kwargs.get("window")
+        n = n_fft or kwargs.get("win_length") or (w.numel() if isinstance(w, torch.Tensor) else None)      # (as stft reads them)
+        _checked_order(formant_order, n if isinstance(n, int) and not isinstance(n, bool) else None, "formant_order")
+    _checked_iter(formant_iter, "formant_iter")
     y = time_stretch(x, rate, n_fft=n_fft, max_iter=max_iter, method=method, phase_lock=phase_lock, lock_tol=lock_tol, **kwargs)
     if orig != sample_rate:
         y = resample(y, orig, sample_rate, lowpass_filter_width, rolloff)
     n = x.shape[-1]
-    if y.shape[-1] >= n:
-        return y[..., :n]
-    return torch.nn.functional.pad(y, (0, n - y.shape[-1]))
+    y = y[..., :n] if y.shape[-1] >= n else torch.nn.functional.pad(y, (0, n - y.shape[-1]))
+    if not preserve_formants:
+        return y
+    stft_kwargs = {k: v for k, v in kwargs.items() if k in _RECOGNISED}
+    return impose_envelope(y, x, n_fft, formant_order or default_envelope_order(sample_rate), formant_iter, **stft_kwargs)
