@@ -205,6 +205,32 @@ int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int3
 int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int64_t batch, int32_t n_freq, int32_t n_frames,
                               int32_t order, int32_t n_iter, int32_t out_log, int32_t is_complex, int32_t frame_major, int32_t dtype,
                               int32_t device, void* hip_stream);
+/* YIN f0 tracking (not in the reference; csrc/kernels_yin.h): the estimator of de Cheveigne & Kawahara 2002 in one launch.  x is
+ * (batch, length), real, of `dtype`, on HIP device `device`; period_out and aper_out are (batch, T) float32, tau_out (batch, T) int32 or
+ * NULL, cmnd_out (batch, T, W + 1) float32 or NULL; enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept between
+ * calls.  With N = frame, W = N / 2, H = hop and xz(i) = x[i] for 0 <= i < length, else 0:
+ *     Frames.      center != 0: T = 1 + length / H, s_m = m H - W ;  center == 0: T = 1 + (length - N) / H, s_m = m H ;
+ *                  f_m[j] = xz(s_m + j), j < N.
+ *     Difference.  d(tau) = sum_{j<W} (f[j] - f[j+tau])^2 = E(0) + E(tau) - 2 r(tau), tau = 0 ... W ;
+ *                  E(tau) = sum_{j=tau}^{tau+W-1} f[j]^2 ;  r(tau) = sum_{j<W} f[j] f[j+tau].
+ *     Normalised.  d'(0) = 1 ;  c(tau) = sum_{k=1}^{tau} d(k) ;  d'(tau) = d(tau) tau / c(tau) where c(tau) > 0, else 1.
+ *     Pick.        tau0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold.  If it exists, tau* = tau0 advanced while
+ *                  tau* + 1 <= tau_max and d'(tau* + 1) < d'(tau*) ; if not, tau* = the first arg-min of d' over the range.
+ *     Refinement.  a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1), q = a - 2 b + c ;  s = (a - c) / (2 q) if q > 0 and |a - c| < q,
+ *                  else 0 ;  period_out = tau* + s, aper_out = b, tau_out = tau*, cmnd_out = d'(0 ... W).  b < threshold is exactly
+ *                  the condition that tau0 existed (a voiced frame).
+ * r goes through a float32 FFT (two complex transforms of length N per frame; the lags 1 ... 8 take d from the literal sum in
+ * float64 instead); E, d and c are float64; d' is rounded once to float32 and the pick runs on those values, the ones cmnd_out
+ * receives, against the float64 threshold; the refinement is float64 from the three float32 values, rounded once.  A silent frame
+ * is d' = 1 throughout, tau* = tau_min and unvoiced.  With cmnd_out given the pick still runs.  Any batch: it is not a launch
+ * dimension of its own.  NaN input is unspecified.  Stateless: a running method is not disturbed.
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL x, period_out or aper_out ; an output that is x or another
+ * output ; batch < 1 ; an unknown dtype ; then SPECINV_EUNSUPPORTED for SPECINV_F64 ; a frame that is not 256, 512, 1024 or 2048 ;
+ * then SPECINV_EINVAL for hop outside 1 ... frame ; a length that gives no frame (length < 1, or length < frame with center == 0) ;
+ * tau_min < 1, tau_max > frame / 2 - 1 or tau_min >= tau_max ; a threshold that is not finite and > 0. */
+int specinv_yin(const void* x, void* period_out, void* aper_out, void* tau_out, void* cmnd_out, int64_t batch, int64_t length,
+                int32_t frame, int32_t hop, int32_t center, int32_t tau_min, int32_t tau_max, double threshold, int32_t dtype,
+                int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

@@ -82,6 +82,8 @@ SIGNATURES = {
                                C.c_int32, C.c_int32, _P]),
     "specinv_spectral_envelope": (C.c_int, [_P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_int32, _P]),
+    "specinv_yin": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32,
+                              C.c_int32, _P]),
     "specinv_wsola": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,

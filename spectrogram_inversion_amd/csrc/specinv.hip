@@ -8,6 +8,7 @@
 #include "kernels_mel_nnls_adjoint.h"
 #include "kernels_hpss.h"
 #include "kernels_envelope.h"
+#include "kernels_yin.h"
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
 #include "kernels_pghi.h"
@@ -370,6 +371,34 @@ int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int
   SI_HIP(guard_.enter(device));
   return envelope_launch((const float*)spec, (float*)out, (const float*)amin, batch, n_freq, n_frames, order, n_iter, out_log != 0,
                          is_complex != 0, frame_major != 0, static_cast<hipStream_t>(hip_stream));
+}
+int specinv_yin(const void* x, void* period_out, void* aper_out, void* tau_out, void* cmnd_out, int64_t batch, int64_t length,
+                int32_t frame, int32_t hop, int32_t center, int32_t tau_min, int32_t tau_max, double threshold, int32_t dtype,
+                int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(x && period_out && aper_out, SPECINV_EINVAL, "specinv_yin: NULL %s", !x ? "x" : !period_out ? "period_out" : "aper_out");
+  {
+    const void* p[5] = {x, period_out, aper_out, tau_out, cmnd_out};
+    static const char* const names[5] = {"x", "period_out", "aper_out", "tau_out", "cmnd_out"};
+    for (int i = 1; i < 5; ++i)
+      for (int j = 0; j < i; ++j)
+        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_yin: %s must not alias %s", names[i], names[j]);
+  }
+  SI_CHECK(batch >= 1, SPECINV_EINVAL, "specinv_yin: batch must be >= 1, got %lld", (long long)batch);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_yin: float32 only");
+  SI_CHECK(frame == 256 || frame == 512 || frame == 1024 || frame == 2048, SPECINV_EUNSUPPORTED,
+           "specinv_yin: frame must be 256, 512, 1024 or 2048, got %d", frame);
+  SI_CHECK(hop >= 1 && hop <= frame, SPECINV_EINVAL, "specinv_yin: hop must be in 1 ... %d, got %d", frame, hop);
+  SI_CHECK(length >= (center ? 1 : frame), SPECINV_EINVAL, "specinv_yin: a length of %lld gives no frame (center %d, frame %d)",
+           (long long)length, center, frame);
+  SI_CHECK(tau_min >= 1 && tau_max <= frame / 2 - 1 && tau_min < tau_max, SPECINV_EINVAL,
+           "specinv_yin: tau_min, tau_max must satisfy 1 <= tau_min < tau_max <= %d, got %d, %d", frame / 2 - 1, tau_min, tau_max);
+  SI_CHECK(std::isfinite(threshold) && threshold > 0, SPECINV_EINVAL, "specinv_yin: threshold must be finite and > 0, got %g", threshold);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  return yin_launch((const float*)x, (float*)period_out, (float*)aper_out, (int32_t*)tau_out, (float*)cmnd_out, batch, length, frame,
+                    hop, center != 0, tau_min, tau_max, threshold, static_cast<hipStream_t>(hip_stream));
 }
 int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
                   int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,

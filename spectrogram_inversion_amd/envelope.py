@@ -1,6 +1,6 @@
 """Spectral envelopes: `spectral_envelope`, the true-envelope estimator of Roebel & Rodet 2005 in one kernel launch
 (csrc/kernels_envelope.h), `impose_envelope`, which makes one waveform carry another's envelope, and
-`default_envelope_order`.  `pitch_shift(..., preserve_formants=True)` is built from them.
+`default_envelope_order` and `envelope_order_for_f0`.  `pitch_shift(..., preserve_formants=True)` is built from them.
 
 `S` is a one-sided spectrogram (F, T) / (B, F, T), real non-negative magnitudes or complex, F = N / 2 + 1 with N = n_fft.  Per
 item and frame:
@@ -35,7 +35,7 @@ from . import _lib
 from ._ingest import ingest
 from .plan import _RECOGNISED, require_gpu
 
-__all__ = ["spectral_envelope", "impose_envelope", "default_envelope_order"]
+__all__ = ["spectral_envelope", "impose_envelope", "default_envelope_order", "envelope_order_for_f0"]
 
 SUPPORTED_N_FFT = (256, 512, 1024, 2048)
 MAX_ITER = 256
@@ -45,13 +45,22 @@ _KINDS = {torch.float16: (torch.float16, False), torch.bfloat16: (torch.bfloat16
 _MAX_BLOCKS = 65535            # workgroups one call of the entry point is given: the wrapper slices the items beyond
 
 
+def envelope_order_for_f0(sample_rate, f0):
+    """`max(1, round(sample_rate / (2 f0)))`: the cepstral order whose cut-off quefrency is half the period of a voice at `f0` Hz,
+    the true-envelope order of Roebel & Rodet - the envelope then follows the formants and not the harmonics.  `yin` measures
+    `f0`; `default_envelope_order(sample_rate)` is this at 300 Hz.  ValueError for an argument that is not a finite number > 0."""
+    for name, v in (("sample_rate", sample_rate), ("f0", f0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (v > 0 and math.isfinite(v)):
+            raise ValueError(f"{name} must be a finite number > 0, got {v!r}")
+    return max(1, round(sample_rate / (2 * f0)))
+
+
 def default_envelope_order(sample_rate):
-    """`max(1, round(sample_rate / 600))`: the cepstral order whose cut-off quefrency is half the period of a 300 Hz voice, so
-    that the envelope follows the formants and not the harmonics of voices up to about there.  A default, not a tuned value: a
-    higher voice wants a lower order, a bass a higher one."""
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, numbers.Real) or not (sample_rate > 0 and math.isfinite(sample_rate)):
-        raise ValueError(f"sample_rate must be a finite number > 0, got {sample_rate!r}")
-    return max(1, round(sample_rate / 600))
+    """`max(1, round(sample_rate / 600))`, which is `envelope_order_for_f0(sample_rate, 300)`: the cepstral order whose cut-off
+    quefrency is half the period of a 300 Hz voice, so that the envelope follows the formants and not the harmonics of voices up
+    to about there.  A default, not a tuned value: a higher voice wants a lower order, a bass a higher one - where the pitch can
+    be measured, `envelope_order_for_f0` with `yin`'s f0 (or `pitch_shift(..., formant_order="f0")`) gives that order."""
+    return envelope_order_for_f0(sample_rate, 300)
 
 
 def _checked_iter(n_iter, name="n_iter"):

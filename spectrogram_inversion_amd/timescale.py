@@ -258,8 +258,14 @@ def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_ite
         impose_envelope(z, x, n_fft, formant_order or default_envelope_order(sample_rate), formant_iter, **stft_kwargs)
 
     (envelope.py) with the STFT arguments among `**kwargs`: `formant_order` is the cepstral order of the envelope (an int in
-    0 ... n_fft / 2; None or 0: the default for the sampling rate) and `formant_iter` the number of true-envelope passes
-    (0 ... 256).  It costs two more STFTs, two envelopes and an inverse STFT, and `spectral_envelope`'s limits apply (float32,
+    0 ... n_fft / 2; None or 0: the default for the sampling rate, a guess for a 300 Hz voice) and `formant_iter` the number of
+    true-envelope passes (0 ... 256).  `formant_order="f0"` measures the pitch instead: with
+
+        f0, voiced, _ = yin(x, sample_rate, fmin=sample_rate / 1000, fmax=sample_rate / 20, frame_length=2048)
+
+    (pitch.py) the order is `min(n_fft // 2, envelope_order_for_f0(sample_rate, median of f0[voiced]))` over the whole batch - one
+    more launch and one read-back - and the default where no frame is voiced; with `preserve_formants=False` nothing is computed.
+    Preserving costs two more STFTs, two envelopes and an inverse STFT, and `spectral_envelope`'s limits apply (float32,
     n_fft 256 ... 2048, one-sided).  With the default `False` nothing changes.
     """
     from .envelope import _checked_iter, _checked_order, default_envelope_order, impose_envelope
@@ -267,7 +273,10 @@ def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_ite
     rate, orig = shift_rate(sample_rate, n_steps, bins_per_octave)
     _checked_lock(phase_lock)
     lock_tol = _checked_lock_tol(lock_tol)
-    if formant_order is not None:
+    if isinstance(formant_order, str):
+        if formant_order != "f0":
+            raise ValueError(f'formant_order must be an int, None or "f0", got {formant_order!r}')
+    elif formant_order is not None:
         w = kwargs.get("window")
         n = n_fft or kwargs.get("win_length") or (w.numel() if isinstance(w, torch.Tensor) else None)      # (as stft reads them)
         _checked_order(formant_order, n if isinstance(n, int) and not isinstance(n, bool) else None, "formant_order")
@@ -280,4 +289,22 @@ def pitch_shift(x, sample_rate, n_steps, bins_per_octave=12, n_fft=None, max_ite
     if not preserve_formants:
         return y
     stft_kwargs = {k: v for k, v in kwargs.items() if k in _RECOGNISED}
+    if formant_order == "f0":
+        formant_order = _order_from_f0(x, sample_rate, n_fft, stft_kwargs)
     return impose_envelope(y, x, n_fft, formant_order or default_envelope_order(sample_rate), formant_iter, **stft_kwargs)
+
+
+def _order_from_f0(x, sample_rate, n_fft, stft_kwargs):
+    """`formant_order="f0"`: the envelope order for the median f0 of the voiced frames of the whole batch (one read-back), at most
+    n_fft // 2; the default order where no frame is voiced"""
+    from .envelope import default_envelope_order, envelope_order_for_f0
+    from .pitch import yin
+    f0, voiced, _ = yin(x, sample_rate, fmin=sample_rate / 1000, fmax=sample_rate / 20, frame_length=2048)
+    # (the median of f0[voiced] without the read-back a boolean index costs: one .item() in all; NaN where nothing is voiced)
+    median = torch.where(voiced, f0, torch.full_like(f0, math.nan)).nanmedian().item() if f0.numel() else math.nan
+    if math.isnan(median):
+        return default_envelope_order(sample_rate)
+    w = stft_kwargs.get("window")
+    n = n_fft or stft_kwargs.get("win_length") or (w.numel() if isinstance(w, torch.Tensor) else None)      # (as stft reads them)
+    order = envelope_order_for_f0(sample_rate, median)
+    return min(n // 2, order) if isinstance(n, int) and not isinstance(n, bool) else order
