@@ -231,6 +231,43 @@ int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int
 int specinv_yin(const void* x, void* period_out, void* aper_out, void* tau_out, void* cmnd_out, int64_t batch, int64_t length,
                 int32_t frame, int32_t hop, int32_t center, int32_t tau_min, int32_t tau_max, double threshold, int32_t dtype,
                 int32_t device, void* hip_stream);
+/* Probabilistic YIN (not in the reference; csrc/kernels_pyin.h; Mauch & Dixon 2014) on the d' that specinv_yin writes to cmnd_out:
+ * two stateless launches on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  tiny = DBL_MIN.
+ * specinv_pyin_obs: cmnd (frames, W + 1) float32, W = frame / 2 -> obs_out (frames, n_bins) float32 and vprob_out (frames,) float32.
+ * `tables` is one float64 device array: s_k (K = n_thresholds entries), w_k (K), cum[0 ... K] with cum[m] = w_1 + ... + w_m,
+ * boltz[r] = (1 - e^-lambda) e^(-lambda r) (n_ranks entries), inv[n] = 1 / (1 - e^(-lambda n)) (n_ranks + 1 entries, inv[0] unused).
+ *     Troughs.     tau in [tau_min, tau_max] with d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1), compared in float32.
+ *     Candidates.  For k = 1 ... K in rising order: the n troughs with d'(tau) < s_k (float64), ranked r = 0 ... n - 1 by rising lag,
+ *                  take p(tau) += (w_k inv[n]) boltz[r].  The first arg-min trough then takes no_trough_prob cum[m], m the number
+ *                  of k with d'(tau) >= s_k.  Float64, not contracted.
+ *     Bins.        A trough with p > 0: period = tau + shift (specinv_yin's refinement), bin = rint(12 bins_per_semitone
+ *                  log2(sample_rate / period / fmin)); below 0 it is bin 0, above n_bins - 1 it is dropped; of several in one bin
+ *                  the largest lag stands.  obs_out[bin] = (float) p, every other entry 0; vprob_out = clip(sum of the standing p, 0, 1).
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL cmnd, tables, obs_out or vprob_out ; an output that is an
+ * input or the other output ; frames < 1 ; an unknown dtype ; then SPECINV_EUNSUPPORTED for SPECINV_F64 ; a frame that is not 256,
+ * 512, 1024 or 2048 ; n_bins outside 1 ... 1024 ; n_thresholds outside 1 ... 1024 ; then SPECINV_EINVAL for tau_min < 1, tau_max >
+ * frame / 2 - 1 or tau_min >= tau_max ; n_ranks < (tau_max - tau_min) / 2 + 1, the troughs a range can hold ; bins_per_semitone < 1 ;
+ * sample_rate or fmin not finite and > 0 ; no_trough_prob outside 0 ... 1. */
+int specinv_pyin_obs(const void* cmnd, const void* tables, void* obs_out, void* vprob_out, int64_t frames, int32_t frame,
+                     int32_t tau_min, int32_t tau_max, int32_t n_thresholds, int32_t n_ranks, int32_t n_bins, int32_t bins_per_semitone,
+                     double sample_rate, double fmin, double no_trough_prob, int32_t dtype, int32_t device, void* hip_stream);
+/* specinv_pyin_viterbi: obs (batch, n_frames, P) float32 and vprob (batch, n_frames) float32, P = n_bins -> states_out (batch,
+ * n_frames) int32, the Viterbi path of the 2 P-state model, one workgroup per item.  State j < P is voiced bin j, P + j unvoiced bin j.
+ * `tables` is one float64 device array: log tri(k), k = 0 ... half_width, then -log Z_i, i < P, with tri(k) = 1 - |k| / (half_width + 1)
+ * and Z_i the sum of tri(j - i) over |j - i| <= half_width, 0 <= j < P.  backptr is scratch, (batch, n_frames, 2 P) int16.
+ *     log B_t[j] = log(obs[t][j] + tiny) voiced, log((1 - vprob[t]) / P + tiny) unvoiced ;  init = 0 voiced, 1 / P unvoiced ;
+ *     A = [[1 - s, s], [s, 1 - s]] (x) tri(j - i) / Z_i inside |j - i| <= half_width, 0 outside, s = switch_prob ;
+ *     delta_0 = log(init + tiny) + log B_0 ;  delta_t[j] = max_i(delta_{t-1}[i] + log(A[i][j] + tiny)) + log B_t[j], the lowest i on
+ *     ties ;  the last frame's arg-max, the lowest index on ties, is walked back.  Float64.  In the band log A is the sum of the
+ *     tables' terms and log(1 - s) or log s; outside it is log tiny, offered by each group's maximum.
+ * ticks_out is NULL or (batch, 3) int64: the 100 MHz wall clock at an item's start, before the walk back and at its end (a
+ * measuring aid).  Any batch.  Before the device is touched, in this order: SPECINV_EINVAL for a NULL obs, vprob, tables, backptr
+ * or states_out ; backptr, states_out or ticks_out equal to an earlier argument ; batch or n_frames < 1 ; an unknown dtype ; then
+ * SPECINV_EUNSUPPORTED for SPECINV_F64 ; n_bins outside 1 ... 1024 ; half_width outside 0 ... 512 ; then SPECINV_EINVAL for a
+ * switch_prob outside (0, 1). */
+int specinv_pyin_viterbi(const void* obs, const void* vprob, const void* tables, void* backptr, void* states_out, void* ticks_out,
+                         int64_t batch, int64_t n_frames, int32_t n_bins, int32_t half_width, double switch_prob, int32_t dtype,
+                         int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

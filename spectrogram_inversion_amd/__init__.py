@@ -27,7 +27,7 @@ from .timescale import phase_vocoder, time_stretch, stretched_frames, pitch_shif
 from .resample import resample                                          # noqa: E402,F401
 from .hpss import hpss, hpss_medians, hpss_audio, harmonic, percussive   # noqa: E402,F401
 from .envelope import spectral_envelope, impose_envelope, default_envelope_order, envelope_order_for_f0   # noqa: E402,F401
-from .pitch import yin, yin_cmnd, yin_frames                            # noqa: E402,F401
+from .pitch import pyin, pyin_bins, pyin_decode, pyin_observations, yin, yin_cmnd, yin_frames   # noqa: E402,F401
 from .tsm import wsola, ola, time_stretch_hpss                          # noqa: E402,F401
 from .pghi import rtpghi                                                # noqa: E402,F401
 from .wiener import consistent_wiener, consistent_wiener_audio          # noqa: E402,F401

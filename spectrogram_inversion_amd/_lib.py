@@ -84,6 +84,9 @@ SIGNATURES = {
                                             C.c_int32, C.c_int32, C.c_int32, _P]),
     "specinv_yin": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32,
                               C.c_int32, _P]),
+    "specinv_pyin_obs": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D,
+                                   _D, _D, C.c_int32, C.c_int32, _P]),
+    "specinv_pyin_viterbi": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _P]),
     "specinv_wsola": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,

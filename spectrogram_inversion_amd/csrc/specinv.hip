@@ -9,6 +9,7 @@
 #include "kernels_hpss.h"
 #include "kernels_envelope.h"
 #include "kernels_yin.h"
+#include "kernels_pyin.h"
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
 #include "kernels_pghi.h"
@@ -399,6 +400,68 @@ int specinv_yin(const void* x, void* period_out, void* aper_out, void* tau_out, 
   SI_HIP(guard_.enter(device));
   return yin_launch((const float*)x, (float*)period_out, (float*)aper_out, (int32_t*)tau_out, (float*)cmnd_out, batch, length, frame,
                     hop, center != 0, tau_min, tau_max, threshold, static_cast<hipStream_t>(hip_stream));
+}
+int specinv_pyin_obs(const void* cmnd, const void* tables, void* obs_out, void* vprob_out, int64_t frames, int32_t frame,
+                     int32_t tau_min, int32_t tau_max, int32_t n_thresholds, int32_t n_ranks, int32_t n_bins, int32_t bins_per_semitone,
+                     double sample_rate, double fmin, double no_trough_prob, int32_t dtype, int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(cmnd && tables && obs_out && vprob_out, SPECINV_EINVAL, "specinv_pyin_obs: NULL %s",
+           !cmnd ? "cmnd" : !tables ? "tables" : !obs_out ? "obs_out" : "vprob_out");
+  SI_CHECK(obs_out != cmnd && vprob_out != cmnd && obs_out != tables && vprob_out != tables && obs_out != vprob_out, SPECINV_EINVAL,
+           "specinv_pyin_obs: an output must not alias an input or the other output");
+  SI_CHECK(frames >= 1, SPECINV_EINVAL, "specinv_pyin_obs: frames must be >= 1, got %lld", (long long)frames);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_pyin_obs: float32 only");
+  SI_CHECK(frame == 256 || frame == 512 || frame == 1024 || frame == 2048, SPECINV_EUNSUPPORTED,
+           "specinv_pyin_obs: frame must be 256, 512, 1024 or 2048, got %d", frame);
+  SI_CHECK(n_bins >= 1 && n_bins <= kPyinMaxBins, SPECINV_EUNSUPPORTED, "specinv_pyin_obs: n_bins must be in 1 ... %d, got %d",
+           kPyinMaxBins, n_bins);
+  SI_CHECK(n_thresholds >= 1 && n_thresholds <= kPyinMaxThresholds, SPECINV_EUNSUPPORTED,
+           "specinv_pyin_obs: n_thresholds must be in 1 ... %d, got %d", kPyinMaxThresholds, n_thresholds);
+  SI_CHECK(tau_min >= 1 && tau_max <= frame / 2 - 1 && tau_min < tau_max, SPECINV_EINVAL,
+           "specinv_pyin_obs: tau_min, tau_max must satisfy 1 <= tau_min < tau_max <= %d, got %d, %d", frame / 2 - 1, tau_min, tau_max);
+  SI_CHECK(n_ranks >= (tau_max - tau_min) / 2 + 1, SPECINV_EINVAL,
+           "specinv_pyin_obs: n_ranks must cover the %d troughs the range can hold, got %d", (tau_max - tau_min) / 2 + 1, n_ranks);
+  SI_CHECK(bins_per_semitone >= 1, SPECINV_EINVAL, "specinv_pyin_obs: bins_per_semitone must be >= 1, got %d", bins_per_semitone);
+  SI_CHECK(std::isfinite(sample_rate) && sample_rate > 0 && std::isfinite(fmin) && fmin > 0, SPECINV_EINVAL,
+           "specinv_pyin_obs: sample_rate and fmin must be finite and > 0, got %g and %g", sample_rate, fmin);
+  SI_CHECK(no_trough_prob >= 0 && no_trough_prob <= 1, SPECINV_EINVAL, "specinv_pyin_obs: no_trough_prob must be in 0 ... 1, got %g",
+           no_trough_prob);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  return pyin_obs_launch((const float*)cmnd, (const double*)tables, (float*)obs_out, (float*)vprob_out, frames, frame, tau_min, tau_max,
+                         n_thresholds, n_ranks, n_bins, bins_per_semitone, sample_rate, fmin, no_trough_prob,
+                         static_cast<hipStream_t>(hip_stream));
+}
+int specinv_pyin_viterbi(const void* obs, const void* vprob, const void* tables, void* backptr, void* states_out, void* ticks_out,
+                         int64_t batch, int64_t n_frames, int32_t n_bins, int32_t half_width, double switch_prob, int32_t dtype,
+                         int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(obs && vprob && tables && backptr && states_out, SPECINV_EINVAL, "specinv_pyin_viterbi: NULL %s",
+           !obs ? "obs" : !vprob ? "vprob" : !tables ? "tables" : !backptr ? "backptr" : "states_out");
+  {
+    const void* p[6] = {obs, vprob, tables, backptr, states_out, ticks_out};
+    static const char* const names[6] = {"obs", "vprob", "tables", "backptr", "states_out", "ticks_out"};
+    for (int i = 3; i < 6; ++i)
+      for (int j = 0; j < i; ++j)
+        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_pyin_viterbi: %s must not alias %s", names[i], names[j]);
+  }
+  SI_CHECK(batch >= 1 && n_frames >= 1, SPECINV_EINVAL, "specinv_pyin_viterbi: batch and n_frames must be >= 1, got %lld and %lld",
+           (long long)batch, (long long)n_frames);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_pyin_viterbi: float32 observations only");
+  SI_CHECK(n_bins >= 1 && n_bins <= kPyinMaxBins, SPECINV_EUNSUPPORTED, "specinv_pyin_viterbi: n_bins must be in 1 ... %d, got %d",
+           kPyinMaxBins, n_bins);
+  SI_CHECK(half_width >= 0 && half_width <= kPyinMaxHalf, SPECINV_EUNSUPPORTED,
+           "specinv_pyin_viterbi: half_width must be in 0 ... %d (a band of at most %d bins), got %d", kPyinMaxHalf,
+           2 * kPyinMaxHalf + 1, half_width);
+  SI_CHECK(switch_prob > 0 && switch_prob < 1, SPECINV_EINVAL, "specinv_pyin_viterbi: switch_prob must be in (0, 1), got %g",
+           switch_prob);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  return pyin_viterbi_launch((const float*)obs, (const float*)vprob, (const double*)tables, (int16_t*)backptr, (int32_t*)states_out,
+                             (int64_t*)ticks_out, batch, n_frames, n_bins, half_width, switch_prob,
+                             static_cast<hipStream_t>(hip_stream));
 }
 int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
                   int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
