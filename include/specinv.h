@@ -268,6 +268,38 @@ int specinv_pyin_obs(const void* cmnd, const void* tables, void* obs_out, void* 
 int specinv_pyin_viterbi(const void* obs, const void* vprob, const void* tables, void* backptr, void* states_out, void* ticks_out,
                          int64_t batch, int64_t n_frames, int32_t n_bins, int32_t half_width, double switch_prob, int32_t dtype,
                          int32_t device, void* hip_stream);
+/* Single-channel speech enhancement (not in the reference; csrc/kernels_enhance.h): the noise-power tracker of Gerkmann & Hendriks
+ * 2012, the decision-directed a-priori SNR and the Wiener or log-spectral-amplitude gain of Ephraim & Malah 1984 / 1985, one
+ * stateless launch on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  spec is (batch, n_freq, n_frames), or
+ * (batch, n_frames, n_freq) with frame_major != 0, real magnitudes or (is_complex != 0) interleaved complex values of `dtype`.
+ * Outputs, each NULL or a device array: noise_out (sigma^2), spp_out (p), gain_out (G), snr_out (xi), real, of `dtype`, in spec's
+ * layout; enhanced_out (G spec), of spec's type and layout; state_out (batch, n_freq, 3) float64, the last frame's sigma^2, Pbar,
+ * A^2 in either layout.  state_in is NULL or such an array: it replaces the start rules.  noise_mode SPECINV_ENHANCE_TRACK runs the
+ * tracker (noise NULL); SPECINV_ENHANCE_NOISE_FULL reads sigma^2 from `noise`, real, of `dtype`, in spec's layout;
+ * SPECINV_ENHANCE_NOISE_PROFILE from `noise` (batch, n_freq), one value per chain.  Per item and bin, frames l = 0 ... T - 1, in
+ * float64 whatever `dtype`, products and sums not contracted; P_l = re^2 + im^2 or m^2; tiny = 1e-300; q(a) = min(a / max(sigma^2,
+ * tiny), 1e300); xi1 = prior_snr, c = xi1 / (1 + xi1):
+ *     Start.    state_in NULL: sigma^2_{-1} = the mean of P_l over the first min(init_frames, T) frames, summed in frame order;
+ *               Pbar_{-1} = 0; the first term of xi_0 is alpha.
+ *     Tracker.  g' = q(P_l) on sigma^2_{l-1} ;  p = 1 / (1 + (1 + xi1) exp(-(g' c))) ;  Pbar_l = alpha_spp Pbar_{l-1} + (1 - alpha_spp) p ;
+ *               if Pbar_l > 0.99: p = min(p, 0.99) ;  sigma^2_l = alpha_pow sigma^2_{l-1} + (1 - alpha_pow) ((1 - p) P_l + p sigma^2_{l-1}).
+ *     Gain.     g = q(P_l), r = q(A^2_{l-1}) on sigma^2_l ;  xi_l = max(alpha r + (1 - alpha) max(g - 1, 0), xi_min) ;  w = xi_l / (1 + xi_l) ;
+ *               SPECINV_ENHANCE_WIENER: G = w ;  SPECINV_ENHANCE_LSA: G = w exp(E1(max(w g, 1e-12)) / 2) ;
+ *               G_l = min(max(G, gain_min), 1) ;  A^2_l = G_l^2 P_l.
+ * E1 is the exponential integral, evaluated to a relative error below 1e-13 on [1e-12, 700] and as 0 beyond.  prior_snr, xi_min
+ * and gain_min are plain ratios, not decibels.  One call on T frames and two calls chained through the state give the same bits.
+ * Any batch, n_freq and n_frames: none is a launch dimension of its own.  NaN input is unspecified.  A running method is not disturbed.
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL spec ; every output NULL ; an unknown noise_mode ; noise
+ * given with SPECINV_ENHANCE_TRACK or NULL without ; noise given with noise_out or spp_out ; a pointer equal to an earlier
+ * argument ; batch, n_freq or n_frames < 1 ; more than 2^58 elements ; init_frames < 1 ; an unknown dtype ; an unknown rule ;
+ * alpha_pow, alpha_spp or alpha outside 0 ... 1 ; prior_snr or xi_min not finite and > 0 ; gain_min outside (0, 1]. */
+enum { SPECINV_ENHANCE_WIENER = 0, SPECINV_ENHANCE_LSA = 1 };
+enum { SPECINV_ENHANCE_TRACK = 0, SPECINV_ENHANCE_NOISE_FULL = 1, SPECINV_ENHANCE_NOISE_PROFILE = 2 };
+int specinv_enhance(const void* spec, const void* noise, const void* state_in, void* noise_out, void* spp_out, void* gain_out,
+                    void* snr_out, void* enhanced_out, void* state_out, int64_t batch, int64_t n_freq, int64_t n_frames,
+                    int32_t init_frames, int32_t noise_mode, int32_t rule, double alpha_pow, double alpha_spp, double prior_snr,
+                    double alpha, double xi_min, double gain_min, int32_t is_complex, int32_t frame_major, int32_t dtype,
+                    int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

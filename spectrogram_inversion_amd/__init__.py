@@ -31,4 +31,5 @@ from .pitch import pyin, pyin_bins, pyin_decode, pyin_observations, yin, yin_cmn
 from .tsm import wsola, ola, time_stretch_hpss                          # noqa: E402,F401
 from .pghi import rtpghi                                                # noqa: E402,F401
 from .wiener import consistent_wiener, consistent_wiener_audio          # noqa: E402,F401
+from .enhance import noise_psd, spectral_gain, denoise                  # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

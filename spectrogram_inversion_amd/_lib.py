@@ -19,6 +19,8 @@ METRICS = {"SC": 0, "SNR": 1, "SER": 2}
 TF_MAG, TF_LOGMEL = 0, 1
 PVOC_LOCK = {None: 0, "identity": 1}
 HPSS_COMPONENTS, HPSS_MASKS, HPSS_MEDIANS = 0, 1, 2
+ENHANCE_RULES = {"wiener": 0, "lsa": 1}
+ENHANCE_TRACK, ENHANCE_NOISE_FULL, ENHANCE_NOISE_PROFILE = 0, 1, 2
 
 
 class StftCfg(C.Structure):
@@ -87,6 +89,8 @@ SIGNATURES = {
     "specinv_pyin_obs": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D,
                                    _D, _D, C.c_int32, C.c_int32, _P]),
     "specinv_pyin_viterbi": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _P]),
+    "specinv_enhance": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, _D, _D, _D, _D,
+                                  _D, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "specinv_wsola": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,
