@@ -300,6 +300,33 @@ int specinv_enhance(const void* spec, const void* noise, const void* state_in, v
                     int32_t init_frames, int32_t noise_mode, int32_t rule, double alpha_pow, double alpha_spp, double prior_snr,
                     double alpha, double xi_min, double gain_min, int32_t is_complex, int32_t frame_major, int32_t dtype,
                     int32_t device, void* hip_stream);
+/* Weighted prediction error dereverberation (not in the reference; csrc/kernels_wpe.h; Nakatani et al. 2010, the offline form),
+ * one stateless launch for all iterations on HIP device `device`, enqueued on hip_stream (NULL: the null stream).  spec and out
+ * are (batch, channels, n_freq, n_frames) interleaved complex values of `dtype`.  Per item and bin f, with K = taps, D = channels K,
+ * x_t = spec[:, f, t] and the stacked past xs_t in C^D, entry (c', k) at row c' K + k = spec[c', f, t - delay - k], zero before frame 0:
+ *     q_t   = mean_c |Y[c, f, t]|^2, Y the previous iteration's result in float64 (never a rounded copy), spec itself in the
+ *             first; or power[f, t] in the first when `power` (batch, n_freq, n_frames) float64 is given
+ *     p_t   = the mean of q over the frames t - psd_context ... t + psd_context that exist
+ *     lam_t = max(p_t, eps max_t p_t, tiny), tiny = the smallest normal double
+ *     R = sum_t xs_t xs_t^H / lam_t ;  P = sum_t xs_t x_t^H / lam_t ;  R += (diag_load tr(R) / D + tiny) I ;  G = R^-1 P
+ *     Y[:, f, t] = x_t - G^H xs_t
+ * repeated n_iter times; out = Y rounded once to `dtype`.  All sums, the factorisation (U D U^H, pivots floored at tiny) and the
+ * solve are float64.  n_iter = 0 gives G = 0 and out = spec.  A silent bin gives G = 0 and out = 0; nothing is NaN for finite input.
+ * filt_out is NULL or (batch, n_freq, D, channels) complex float64: G, entry [c' K + k][c] the weight of channel c' at lag delay + k
+ * in the prediction of channel c.  lam (batch, n_freq, n_frames) float64 receives the last lam and is the estimate's work array:
+ * never NULL when estimating.  scratch is a second such array, needed when psd_context > 0.
+ * Filter-only mode: filt_in, an array like filt_out, is given; nothing is estimated and out = spec - G^H xs, by the same
+ * instructions as the estimating call's last pass (the same bits when G came from it); power, filt_out and lam must be NULL.
+ * Any batch, n_freq, n_frames and delay; n_iter <= 100 and psd_context <= 64 (the context mean is 2 psd_context + 1 reads a frame:
+ * the launch's length stays bounded); an item's result does not depend on the batch around it.
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL spec or out ; filt_in given with power, filt_out or lam ;
+ * lam NULL without filt_in ; psd_context > 0 without scratch (and without filt_in) ; out, filt_out, lam or scratch equal to an
+ * earlier argument ; batch, channels, n_freq or n_frames < 1 ; more than 2^51 elements a channel ; taps < 1 ; delay < 1 ; n_iter or
+ * psd_context < 0 ; eps or diag_load negative or not finite ; an unknown dtype ; then SPECINV_EUNSUPPORTED for channels taps > 64 ;
+ * n_iter > 100 or psd_context > 64. */
+int specinv_wpe(const void* spec, const void* power, const void* filt_in, void* out, void* filt_out, void* lam, void* scratch,
+                int64_t batch, int32_t channels, int64_t n_freq, int64_t n_frames, int32_t taps, int64_t delay, int32_t n_iter,
+                int64_t psd_context, double eps, double diag_load, int32_t dtype, int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

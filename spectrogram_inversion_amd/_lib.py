@@ -91,6 +91,8 @@ SIGNATURES = {
     "specinv_pyin_viterbi": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _P]),
     "specinv_enhance": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, _D, _D, _D, _D,
                                   _D, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "specinv_wpe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, C.c_int32, _I64, _I64, C.c_int32, _I64, C.c_int32, _I64, _D, _D, C.c_int32,
+                              C.c_int32, _P]),
     "specinv_wsola": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,
