@@ -327,6 +327,34 @@ int specinv_enhance(const void* spec, const void* noise, const void* state_in, v
 int specinv_wpe(const void* spec, const void* power, const void* filt_in, void* out, void* filt_out, void* lam, void* scratch,
                 int64_t batch, int32_t channels, int64_t n_freq, int64_t n_frames, int32_t taps, int64_t delay, int32_t n_iter,
                 int64_t psd_context, double eps, double diag_load, int32_t dtype, int32_t device, void* hip_stream);
+/* Mask-based beamforming (not in the reference; csrc/kernels_beamform.h), one stateless launch on HIP device `device`, enqueued on
+ * hip_stream (NULL: the null stream).  spec is (batch, channels, n_freq, n_frames) interleaved complex values of `dtype`, out
+ * (batch, n_freq, n_frames) of the same.  Per item and bin f, with C = channels, x_t = spec[:, f, t], m = mask_target[f, t] (1 when
+ * NULL), n = mask_noise[f, t] (1 - m when NULL), both (batch, n_freq, n_frames) float64 and non-negative:
+ *     Phi(m)  = sum_t m_t x_t x_t^H / max(sum_t m_t, tiny), tiny = the smallest normal double ;  Phi_s = Phi(m), Phi_n = Phi(n)
+ *     load(A) = A + (diag_load Re tr(A) / C + tiny) I
+ *     SOUDEN:     A = load(Phi_n) ;  N = A^-1 Phi_s ;  w = N[:, ref_channel] / max(Re tr(N), tiny)
+ *     RTF_POWER:  A, N as above ;  v = N[:, ref_channel] ;  n_power_iter - 1 times v <- N (v / max(|Re v|_inf, |Im v|_inf, tiny)) ;
+ *                 a = A v ;  w = v conj(a[ref_channel]) / max(Re(a^H v), tiny)
+ *     MWF:        A = load(Phi_s + mu Phi_n) ;  w = A^-1 Phi_s[:, ref_channel]
+ *     out[f, t] = w^H x_t, rounded once to `dtype`
+ * All sums, the factorisation (U D U^H, pivots floored at tiny) and the solves are float64.  A silent bin or an all-zero mask gives
+ * Phi = 0, w = 0 and out = 0; nothing is NaN for finite input.  scm_target / scm_noise are NULL or (batch, n_freq, C, C) complex
+ * float64 and receive Phi_s / Phi_n before the loading, exactly Hermitian.  weights_out is NULL or (batch, n_freq, C) complex float64: w.
+ * Covariance-only mode: out and weights_out NULL; only the sums run (mask_target may then be NULL: all ones).
+ * Filter-only mode: weights_in, an array like weights_out, is given; nothing is estimated and out = w^H x by the same instructions
+ * as the estimating call's (the same bits when w came from it); the masks, weights_out and the covariances must be NULL.
+ * Any batch, n_freq and n_frames; an item's result does not depend on the batch around it or on the mode.
+ * Before the device is touched, in this order: SPECINV_EINVAL for a NULL spec ; weights_in given without out or with a mask,
+ * weights_out or a covariance ; no result asked for ; out or weights_out without mask_target (and without weights_in) ; out,
+ * weights_out, scm_target or scm_noise equal to an earlier argument ; batch, channels, n_freq or n_frames < 1 ; more than 2^51
+ * elements a channel ; an unknown solution ; ref_channel outside [0, channels) ; n_power_iter < 1 ; diag_load or mu negative or not
+ * finite ; an unknown dtype ; then SPECINV_EUNSUPPORTED for channels > 16 ; n_power_iter > 64. */
+enum { SPECINV_BEAMFORM_SOUDEN = 0, SPECINV_BEAMFORM_RTF_POWER = 1, SPECINV_BEAMFORM_MWF = 2 };
+int specinv_beamform(const void* spec, const void* mask_target, const void* mask_noise, const void* weights_in, void* out,
+                     void* weights_out, void* scm_target, void* scm_noise, int64_t batch, int32_t channels, int64_t n_freq,
+                     int64_t n_frames, int32_t solution, int32_t ref_channel, int32_t n_power_iter, double diag_load, double mu,
+                     int32_t dtype, int32_t device, void* hip_stream);
 /* Time-domain time-scale modification (not in the reference; csrc/kernels_wsola.h): waveform-similarity overlap-add, and plain
  * overlap-add at tol = 0.  x (batch, n_in) -> y (batch, n_out) and lags (batch, n_frames) int32, device arrays on HIP device
  * `device`, x, window (frame entries) and y of `dtype`, enqueued on hip_stream (NULL: the null stream).  No plan: nothing is kept

@@ -33,4 +33,5 @@ from .pghi import rtpghi                                                # noqa: 
 from .wiener import consistent_wiener, consistent_wiener_audio          # noqa: E402,F401
 from .enhance import noise_psd, spectral_gain, denoise                  # noqa: E402,F401
 from .dereverb import wpe, wpe_apply, dereverb                          # noqa: E402,F401
+from .beamform import spatial_covariance, beamform, beamform_apply, beamform_audio   # noqa: E402,F401
 from .plan import set_exact_projection, has_approx                      # noqa: E402,F401

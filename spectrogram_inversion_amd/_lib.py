@@ -21,6 +21,7 @@ PVOC_LOCK = {None: 0, "identity": 1}
 HPSS_COMPONENTS, HPSS_MASKS, HPSS_MEDIANS = 0, 1, 2
 ENHANCE_RULES = {"wiener": 0, "lsa": 1}
 ENHANCE_TRACK, ENHANCE_NOISE_FULL, ENHANCE_NOISE_PROFILE = 0, 1, 2
+BEAMFORM_SOLUTIONS = {"souden": 0, "rtf_power": 1, "mwf": 2}
 
 
 class StftCfg(C.Structure):
@@ -93,6 +94,8 @@ SIGNATURES = {
                                   _D, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "specinv_wpe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, C.c_int32, _I64, _I64, C.c_int32, _I64, C.c_int32, _I64, _D, _D, C.c_int32,
                               C.c_int32, _P]),
+    "specinv_beamform": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int32, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, _D, _D,
+                                   C.c_int32, C.c_int32, _P]),
     "specinv_wsola": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 _P]),
     "specinv_pghi": (C.c_int, [_P, _P, _P, _P, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, C.c_int32, C.c_int32,

@@ -12,6 +12,7 @@
 #include "kernels_pyin.h"
 #include "kernels_enhance.h"
 #include "kernels_wpe.h"
+#include "kernels_beamform.h"
 #include "kernels_resample.h"
 #include "kernels_wsola.h"
 #include "kernels_pghi.h"
@@ -584,6 +585,66 @@ int specinv_wpe(const void* spec, const void* power, const void* filt_in, void* 
   a.eps = eps;
   a.diag_load = diag_load;
   return wpe_launch(a, dtype == SPECINV_F64, static_cast<hipStream_t>(hip_stream));
+}
+int specinv_beamform(const void* spec, const void* mask_target, const void* mask_noise, const void* weights_in, void* out,
+                     void* weights_out, void* scm_target, void* scm_noise, int64_t batch, int32_t channels, int64_t n_freq,
+                     int64_t n_frames, int32_t solution, int32_t ref_channel, int32_t n_power_iter, double diag_load, double mu,
+                     int32_t dtype, int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec, SPECINV_EINVAL, "specinv_beamform: NULL spec");
+  SI_CHECK(weights_in == nullptr || (mask_target == nullptr && mask_noise == nullptr && weights_out == nullptr && scm_target == nullptr &&
+                                     scm_noise == nullptr && out != nullptr),
+           SPECINV_EINVAL,
+           "specinv_beamform: with weights_in given nothing is estimated: out is needed, the masks, weights_out and the covariances "
+           "must be NULL");
+  SI_CHECK(weights_in != nullptr || out != nullptr || weights_out != nullptr || scm_target != nullptr || scm_noise != nullptr, SPECINV_EINVAL,
+           "specinv_beamform: no result is asked for");
+  SI_CHECK(weights_in != nullptr || mask_target != nullptr || (out == nullptr && weights_out == nullptr), SPECINV_EINVAL,
+           "specinv_beamform: weights need mask_target");
+  {
+    const void* p[8] = {spec, mask_target, mask_noise, weights_in, out, weights_out, scm_target, scm_noise};
+    static const char* const names[8] = {"spec", "mask_target", "mask_noise", "weights_in", "out", "weights_out", "scm_target", "scm_noise"};
+    for (int i = 4; i < 8; ++i)
+      for (int j = 0; j < i; ++j)
+        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_beamform: %s must not alias %s", names[i], names[j]);
+  }
+  SI_CHECK(batch >= 1 && channels >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
+           "specinv_beamform: batch, channels, n_freq and n_frames must be >= 1, got %lld, %d, %lld and %lld", (long long)batch, channels,
+           (long long)n_freq, (long long)n_frames);
+  SI_CHECK(batch <= (INT64_MAX >> 12) / n_freq / n_frames, SPECINV_EINVAL,
+           "specinv_beamform: %lld x %lld x %lld elements a channel are too many", (long long)batch, (long long)n_freq, (long long)n_frames);
+  SI_CHECK(solution == SPECINV_BEAMFORM_SOUDEN || solution == SPECINV_BEAMFORM_RTF_POWER || solution == SPECINV_BEAMFORM_MWF, SPECINV_EINVAL,
+           "specinv_beamform: unknown solution %d", solution);
+  SI_CHECK(ref_channel >= 0 && ref_channel < channels, SPECINV_EINVAL, "specinv_beamform: ref_channel must be in [0, %d), got %d", channels,
+           ref_channel);
+  SI_CHECK(n_power_iter >= 1, SPECINV_EINVAL, "specinv_beamform: n_power_iter must be >= 1, got %d", n_power_iter);
+  SI_CHECK(diag_load >= 0 && std::isfinite(diag_load) && mu >= 0 && std::isfinite(mu), SPECINV_EINVAL,
+           "specinv_beamform: diag_load and mu must be finite and >= 0, got %g and %g", diag_load, mu);
+  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
+  SI_CHECK(channels <= kBfMaxChannels, SPECINV_EUNSUPPORTED, "specinv_beamform: channels must be <= %d, got %d", kBfMaxChannels, channels);
+  SI_CHECK(n_power_iter <= kBfMaxPowerIter, SPECINV_EUNSUPPORTED, "specinv_beamform: n_power_iter must be <= %d, got %d", kBfMaxPowerIter,
+           n_power_iter);
+  DeviceGuard guard_;
+  SI_HIP(guard_.enter(device));
+  BfArgs a;
+  a.spec = spec;
+  a.mask_t = (const double*)mask_target;
+  a.mask_n = (const double*)mask_noise;
+  a.w_in = weights_in;
+  a.out = out;
+  a.w_out = weights_out;
+  a.scm_t = scm_target;
+  a.scm_n = scm_noise;
+  a.batch = batch;
+  a.n_freq = n_freq;
+  a.n_frames = n_frames;
+  a.channels = channels;
+  a.solution = solution;
+  a.ref = ref_channel;
+  a.n_power_iter = n_power_iter;
+  a.diag_load = diag_load;
+  a.mu = mu;
+  return beamform_launch(a, dtype == SPECINV_F64, static_cast<hipStream_t>(hip_stream));
 }
 int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
                   int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
