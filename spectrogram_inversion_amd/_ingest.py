@@ -9,9 +9,30 @@ Needs torch only, not the native library.
 """
 from __future__ import annotations
 
+import numbers
+
 import torch
 
 ALIGN = 16          # bytes: the vector kernels load 16 bytes per lane, the wave kernels pair elements by index parity
+
+
+# The predicates the wrappers' argument checks share (each wrapper words its own error).
+def is_int(v) -> bool:
+    """an int that is no bool"""
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def is_real(v) -> bool:
+    """a real number that is no bool (NaN and the infinities included)"""
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def broadcasts_to(shape, want) -> bool:
+    want = tuple(want)
+    try:
+        return torch.broadcast_shapes(tuple(shape), want) == want
+    except RuntimeError:
+        return False
 
 
 def ingest(t: torch.Tensor, device, dtype) -> torch.Tensor:

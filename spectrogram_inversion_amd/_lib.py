@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SPECINV_LIB selects a variant library built with build_lib(extra_flags=..., out=...) (development only)
 LIB_PATH = os.environ.get("SPECINV_LIB") or os.path.join(_PKG, "libspecinv.so")
@@ -217,3 +219,12 @@ def check(code: int):
     if code == EUNSUPPORTED:
         raise NotImplementedError(msg)
     raise SpecinvError(code, msg)
+
+
+def call_op(name: str, args, f64: bool, device):
+    """Call the plan-free entry point `name` on `device`'s current stream and `check` its code.  `args` are the arguments in
+    front of the (dtype code, device index, stream) triple all of these signatures end in: a tensor passes as its data pointer,
+    None as NULL, a number as it is."""
+    stream = torch.cuda.current_stream(device)
+    argv = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    check(getattr(load(), name)(*argv, F64 if f64 else F32, stream.device.index, C.c_void_p(stream.cuda_stream)))

@@ -25,14 +25,12 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-import numbers
 
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import broadcasts_to, ingest, is_int, is_real
 from .plan import _RECOGNISED, require_gpu
 
 __all__ = ["spatial_covariance", "beamform", "beamform_apply", "beamform_audio"]
@@ -68,11 +66,7 @@ def _checked_mask(mask, name, want, what):
         raise TypeError(f"{name} must be a torch.Tensor")
     if mask.dtype not in _REAL:
         raise TypeError(f"{name} must be real (float16 / bfloat16 / float32 / float64), got dtype {mask.dtype}")
-    try:
-        ok = torch.broadcast_shapes(tuple(mask.shape), want) == want
-    except RuntimeError:
-        ok = False
-    if not ok:
+    if not broadcasts_to(mask.shape, want):
         raise ValueError(f"{name} of shape {tuple(mask.shape)} does not broadcast to {want}, spec's shape without the channel axis")
     if torch.is_grad_enabled() and mask.requires_grad:
         raise NotImplementedError(f"{what} is not differentiable; detach the inputs")
@@ -83,16 +77,16 @@ def _checked_mask(mask, name, want, what):
 def _checked_params(solution, ref_channel, channels, diag_load, n_power_iter, mu):
     if solution not in _lib.BEAMFORM_SOLUTIONS:
         raise ValueError(f"solution must be one of {SOLUTIONS}, got {solution!r}")
-    if isinstance(ref_channel, bool) or not isinstance(ref_channel, int):
+    if not is_int(ref_channel):
         raise TypeError(f"ref_channel must be an int, got {ref_channel!r}")
     if channels is not None and not 0 <= ref_channel < channels:
         raise ValueError(f"ref_channel must be in [0, {channels}), got {ref_channel}")
-    if isinstance(n_power_iter, bool) or not isinstance(n_power_iter, int) or n_power_iter < 1:
+    if not is_int(n_power_iter) or n_power_iter < 1:
         raise ValueError(f"n_power_iter must be an int >= 1, got {n_power_iter!r}")
     if n_power_iter > MAX_POWER_ITER:
         raise NotImplementedError(f"n_power_iter must be <= {MAX_POWER_ITER} (the iterations run inside the one launch), got {n_power_iter}")
     for v, name in ((diag_load, "diag_load"), (mu, "mu")):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (v >= 0 and math.isfinite(v)):
+        if not is_real(v) or not (v >= 0 and math.isfinite(v)):
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     return _lib.BEAMFORM_SOLUTIONS[solution], ref_channel, float(diag_load), n_power_iter, float(mu)
 
@@ -105,7 +99,6 @@ def _launch(spec, lead, channels, n_freq, n_frames, mask_t, mask_n, weights, par
         return (z(y_shape, spec.dtype) if want_y else None, z(w_shape, torch.complex128) if want_w else None,
                 z(s_shape, torch.complex128) if want_scm else None, z(s_shape, torch.complex128) if want_scm and want_y else None)
     device = require_gpu(spec.device)
-    lib = _lib.load()
     s4 = ingest(spec.reshape((-1, channels, n_freq, n_frames)), device, spec.dtype)
     batch = s4.shape[0]
     as_mask = lambda m: None if m is None else ingest(m.expand(y_shape).reshape(batch, n_freq, n_frames), device, torch.float64)   # noqa: E731
@@ -117,12 +110,8 @@ def _launch(spec, lead, channels, n_freq, n_frames, mask_t, mask_n, weights, par
     scm_t = new(want_scm, (batch, n_freq, channels, channels), torch.complex128)
     scm_n = new(want_scm and want_y, (batch, n_freq, channels, channels), torch.complex128)      # (not for spatial_covariance)
     solution, ref, diag_load, n_power_iter, mu = params
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_beamform(ptr(s4), ptr(mt), ptr(mn), ptr(w_in), ptr(out), ptr(w_out), ptr(scm_t), ptr(scm_n), batch, channels,
-                                    n_freq, n_frames, solution, ref, n_power_iter, diag_load, mu,
-                                    _lib.F32 if spec.dtype == torch.complex64 else _lib.F64, stream.device.index,
-                                    C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_beamform", (s4, mt, mn, w_in, out, w_out, scm_t, scm_n, batch, channels, n_freq, n_frames, solution, ref,
+                                      n_power_iter, diag_load, mu), spec.dtype != torch.complex64, device)
     back = lambda t, shape: None if t is None else t.reshape(shape).to(device=spec.device)       # noqa: E731
     return back(out, y_shape), back(w_out, w_shape), back(scm_t, s_shape), back(scm_n, s_shape)
 

@@ -431,7 +431,4 @@ __global__ __launch_bounds__(kBfThreads) void k_beamform(const BfArgs a) {
   }
 }
 
-// (tu_beamform.hip)
-int beamform_launch(const BfArgs& a, bool is_double, hipStream_t stream);
-
 }  // namespace specinv

@@ -386,7 +386,4 @@ __global__ __launch_bounds__(kEnhThreads) void k_enhance(const EnhArgs a) {
     enh_walk_bin_major<T, CPLX, RULE>(a, enh_lds);
 }
 
-// (tu_enhance.hip)
-int enhance_launch(const EnhArgs& a, bool is_double, bool is_complex, bool frame_major, int rule, hipStream_t stream);
-
 }  // namespace specinv

@@ -158,9 +158,4 @@ __global__ void __launch_bounds__(kEnvThreads) k_spectral_envelope(EnvArgs a, in
   }
 }
 
-// Host side (tu_envelope.hip): the arguments are checked by the entry point.  Items and tiles are one flattened grid, in as many
-// launches as 2^22 workgroups each take.
-int envelope_launch(const float* spec, float* out, const float* amin, int64_t batch, int n_freq, int n_frames, int order, int n_iter,
-                    bool out_log, bool is_complex, bool frame_major, hipStream_t stream);
-
 }  // namespace specinv

@@ -214,10 +214,4 @@ __global__ void __launch_bounds__(kHpssThreads) k_hpss(const T* __restrict__ spe
   }
 }
 
-// Host side (tu_hpss.hip): the arguments are checked by the entry point.  Batch and the two tile counts are one flattened grid, in
-// as many launches as 2^22 workgroups each take.
-template <typename T>
-int hpss_launch(const T* spec, T* out_a, T* out_b, int64_t batch, int n_freq, int n_frames, int k_h, int k_p, double power,
-                double m_h, double m_p, int mode, bool is_complex, hipStream_t stream);
-
 }  // namespace specinv

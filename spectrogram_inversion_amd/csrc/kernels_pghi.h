@@ -393,9 +393,4 @@ __global__ void __launch_bounds__(NT) k_pghi(const T* __restrict__ mag, cplx<T>*
   }
 }
 
-// Host side (tu_pghi.hip): the arguments are checked by the entry point.  One launch; the grid is min(batch, 2^16) workgroups.
-template <typename T>
-int pghi_launch(const T* mag, cplx<T>* out, double* phase_out, int8_t* parents_out, int64_t batch, int n_freq, int n_frames,
-                int n_fft, int hop, double gamma, double tol, hipStream_t stream);
-
 }  // namespace specinv

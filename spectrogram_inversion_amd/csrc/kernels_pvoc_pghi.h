@@ -301,9 +301,4 @@ __global__ void __launch_bounds__(NT) k_pvoc_pghi(const cplx<T>* __restrict__ in
   }
 }
 
-// Host side (tu_pvoc_pghi.hip): the arguments are checked by the entry point.  One launch; the grid is min(batch, 2^16) workgroups.
-template <typename T>
-int pvoc_pghi_launch(const cplx<T>* in, cplx<T>* out, int8_t* parents_out, int64_t batch, int n_freq, int n_in, int n_out,
-                     int n_fft, int hop, double rate, double tol, hipStream_t stream);
-
 }  // namespace specinv

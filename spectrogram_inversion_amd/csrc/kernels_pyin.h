@@ -380,11 +380,4 @@ __global__ void __launch_bounds__(kPyinMaxBins) k_pyin_viterbi(PyinVitArgs a) {
   }
 }
 
-// Host side (tu_pyin.hip): the arguments are checked by the entry points.
-int pyin_obs_launch(const float* cmnd, const double* tables, float* obs, float* vprob, int64_t frames, int frame, int tau_min,
-                    int tau_max, int n_thr, int n_ranks, int n_bins, int bins_per_semitone, double sample_rate, double fmin,
-                    double no_trough, hipStream_t stream);
-int pyin_viterbi_launch(const float* obs, const float* vprob, const double* tables, int16_t* backptr, int32_t* states, int64_t* ticks,
-                        int64_t batch, int64_t n_frames, int n_bins, int half, double switch_prob, hipStream_t stream);
-
 }  // namespace specinv

@@ -114,10 +114,4 @@ __global__ void __launch_bounds__(kResampleTile) k_resample(const T* __restrict_
   y[row * a.n_out + m] = (T)(a.delta * acc);
 }
 
-// Host side (tu_resample.hip): x (batch, n_in) -> y (batch, n_out), the ratio reduced and n_out checked by the caller.  The batch
-// is part of grid x, in as many launches as 2^22 workgroups each take.
-template <typename T>
-int resample_launch(const T* x, T* y, int64_t batch, int64_t n_in, int64_t n_out, int64_t o, int64_t n, int width, double rolloff,
-                    hipStream_t stream);
-
 }  // namespace specinv

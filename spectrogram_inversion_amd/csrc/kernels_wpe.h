@@ -487,7 +487,4 @@ __global__ __launch_bounds__(kWpeThreads) void k_wpe(const WpeArgs a) {
   }
 }
 
-// (tu_wpe.hip)
-int wpe_launch(const WpeArgs& a, bool is_double, hipStream_t stream);
-
 }  // namespace specinv

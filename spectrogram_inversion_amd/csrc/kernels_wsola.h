@@ -222,10 +222,4 @@ __global__ void __launch_bounds__(kWsolaTile) k_wsola_ola(const T* __restrict__ 
   y[item * a.n_out + j] = (T)(acc / (ow >= 1e-3 ? ow : 1.0));
 }
 
-// Host side (tu_wsola.hip): the arguments are checked by the entry point.  lags is always written (zeros without a chain: tol 0
-// or one frame).  Batch is part of grid x, in as many launches as 2^22 workgroups each take.
-template <typename T>
-int wsola_launch(const T* x, const int64_t* centres, const T* window, int32_t* lags, T* y, int64_t batch, int64_t n_in,
-                 int64_t n_out, int n_frames, int frame, int hop, int tol, hipStream_t stream);
-
 }  // namespace specinv

@@ -250,9 +250,4 @@ __global__ void __launch_bounds__(kYinThreads) k_yin(YinArgs a, int64_t block0) 
   }
 }
 
-// Host side (tu_yin.hip): the arguments are checked by the entry point.  Items and their groups of four frames are one flattened grid,
-// in as many launches as 2^22 workgroups each take.
-int yin_launch(const float* x, float* period, float* aper, int32_t* tau, float* cmnd, int64_t batch, int64_t length, int frame,
-               int hop, bool center, int tau_min, int tau_max, double threshold, hipStream_t stream);
-
 }  // namespace specinv

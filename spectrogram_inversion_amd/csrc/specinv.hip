@@ -1,22 +1,13 @@
-// libspecinv.so - C ABI entry points (include/specinv.h).  gfx950 only.
+// libspecinv.so - the plan and its C ABI entry points (include/specinv.h); the plan-free ops have theirs in their tu_*.hip.
+// gfx950 only.
 #include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <vector>
 
+#include "entry.h"
 #include "kernels_mel_nnls.h"
 #include "kernels_mel_nnls_adjoint.h"
-#include "kernels_hpss.h"
-#include "kernels_envelope.h"
-#include "kernels_yin.h"
-#include "kernels_pyin.h"
-#include "kernels_enhance.h"
-#include "kernels_wpe.h"
-#include "kernels_beamform.h"
-#include "kernels_resample.h"
-#include "kernels_wsola.h"
-#include "kernels_pghi.h"
-#include "kernels_pvoc_pghi.h"
 #include "plan_impl.h"
 
 namespace specinv {
@@ -128,30 +119,6 @@ int PlanBase::run_loop(int max_iter, int eva_iter, double tol, int metric, speci
 }  // namespace specinv
 
 using namespace specinv;
-
-// Calls run on the plan's device; the calling thread's current device (which torch reads back with hipGetDevice) is
-// restored on every return path.
-struct DeviceGuard {
-  int prev = -1, want = -1;
-  hipError_t enter(int device, int64_t* sink = nullptr) {
-    want = device;
-    bytes_sink() = sink;
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) {
-      prev = -1;
-      return e;
-    }
-    if (prev == want) {
-      prev = -1;                // nothing to restore
-      return hipSuccess;
-    }
-    return hipSetDevice(want);
-  }
-  ~DeviceGuard() {
-    bytes_sink() = nullptr;
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 #define PLAN_OR_FAIL(p) SI_CHECK((p) != nullptr && (p)->impl, SPECINV_EINVAL, "plan is NULL")
 
@@ -288,444 +255,6 @@ int specinv_phase_vocoder_locked(specinv_plan* plan, const void* spec_in, int32_
            plan->impl->cfg.n_frames, n_frames_in, rate, (long long)want);
   ENTER(plan);
   return plan->impl->phase_vocoder_locked(spec_in, n_frames_in, rate, spec_out);
-}
-int specinv_resample(const void* x, void* y, int64_t batch, int64_t n_in, int64_t n_out, int64_t orig_freq, int64_t new_freq,
-                     int32_t lowpass_filter_width, double rolloff, int32_t dtype, int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched)
-  SI_CHECK(x && y, SPECINV_EINVAL, "specinv_resample: NULL %s", x ? "y" : "x");
-  SI_CHECK(x != y, SPECINV_EINVAL, "specinv_resample: y must not alias x");
-  SI_CHECK(batch >= 1 && n_in >= 1, SPECINV_EINVAL, "specinv_resample: batch and n_in must be >= 1, got %lld and %lld",
-           (long long)batch, (long long)n_in);
-  SI_CHECK(orig_freq >= 1 && new_freq >= 1, SPECINV_EINVAL, "specinv_resample: orig_freq and new_freq must be >= 1, got %lld and %lld",
-           (long long)orig_freq, (long long)new_freq);
-  SI_CHECK(lowpass_filter_width >= 1, SPECINV_EINVAL, "lowpass_filter_width must be >= 1, got %d", lowpass_filter_width);
-  SI_CHECK(rolloff > 0 && rolloff <= 1, SPECINV_EINVAL, "rolloff must be in (0, 1], got %g", rolloff);
-  int64_t g = orig_freq, t = new_freq;
-  while (t != 0) {
-    const int64_t u = g % t;
-    g = t;
-    t = u;
-  }
-  const int64_t o = orig_freq / g, n = new_freq / g;
-  const __int128 want = ((__int128)n * n_in + o - 1) / o;
-  // (the kernel forms m * o for every output m in 64 bits)
-  SI_CHECK(want < ((__int128)1 << 62) && want * o < ((__int128)1 << 62), SPECINV_EINVAL,
-           "specinv_resample: %lld samples at %lld:%lld index beyond 62 bits", (long long)n_in, (long long)o, (long long)n);
-  SI_CHECK((__int128)n_out == want, SPECINV_EINVAL, "specinv_resample: n_out is %lld, %lld samples at %lld:%lld give %lld",
-           (long long)n_out, (long long)n_in, (long long)o, (long long)n, (long long)want);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (o == n) {                           // the same rate: a copy
-    SI_HIP(hipMemcpyAsync(y, x, (size_t)batch * (size_t)n_in * (dtype == SPECINV_F32 ? 4 : 8), hipMemcpyDeviceToDevice, stream));
-    return SPECINV_OK;
-  }
-  if (dtype == SPECINV_F32)
-    return resample_launch<float>((const float*)x, (float*)y, batch, n_in, n_out, o, n, lowpass_filter_width, rolloff, stream);
-  return resample_launch<double>((const double*)x, (double*)y, batch, n_in, n_out, o, n, lowpass_filter_width, rolloff, stream);
-}
-int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames, int32_t win_harm,
-                 int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode, int32_t is_complex,
-                 int32_t dtype, int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec && out_a && out_b, SPECINV_EINVAL, "specinv_hpss: NULL %s", !spec ? "spec" : !out_a ? "out_a" : "out_b");
-  SI_CHECK(out_a != spec && out_b != spec && out_a != out_b, SPECINV_EINVAL, "specinv_hpss: %s",
-           out_a == out_b ? "out_b must not alias out_a" : "an output must not alias spec");
-  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
-           "specinv_hpss: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
-  SI_CHECK(win_harm >= 1 && win_harm <= kHpssMaxWin && (win_harm & 1), SPECINV_EINVAL,
-           "specinv_hpss: win_harm must be odd in 1 ... %d, got %d", kHpssMaxWin, win_harm);
-  SI_CHECK(win_perc >= 1 && win_perc <= kHpssMaxWin && (win_perc & 1), SPECINV_EINVAL,
-           "specinv_hpss: win_perc must be odd in 1 ... %d, got %d", kHpssMaxWin, win_perc);
-  SI_CHECK(power > 0, SPECINV_EINVAL, "specinv_hpss: power must be > 0 (inf included), got %g", power);
-  SI_CHECK(margin_harm >= 1 && std::isfinite(margin_harm), SPECINV_EINVAL, "specinv_hpss: margin_harm must be finite and >= 1, got %g",
-           margin_harm);
-  SI_CHECK(margin_perc >= 1 && std::isfinite(margin_perc), SPECINV_EINVAL, "specinv_hpss: margin_perc must be finite and >= 1, got %g",
-           margin_perc);
-  SI_CHECK(out_mode == SPECINV_HPSS_COMPONENTS || out_mode == SPECINV_HPSS_MASKS || out_mode == SPECINV_HPSS_MEDIANS, SPECINV_EINVAL,
-           "specinv_hpss: out_mode must be SPECINV_HPSS_COMPONENTS, _MASKS or _MEDIANS, got %d", out_mode);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (dtype == SPECINV_F32)
-    return hpss_launch<float>((const float*)spec, (float*)out_a, (float*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
-                              margin_harm, margin_perc, out_mode, is_complex != 0, stream);
-  return hpss_launch<double>((const double*)spec, (double*)out_a, (double*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
-                             margin_harm, margin_perc, out_mode, is_complex != 0, stream);
-}
-int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int64_t batch, int32_t n_freq, int32_t n_frames,
-                              int32_t order, int32_t n_iter, int32_t out_log, int32_t is_complex, int32_t frame_major, int32_t dtype,
-                              int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec && out && amin, SPECINV_EINVAL, "specinv_spectral_envelope: NULL %s", !spec ? "spec" : !out ? "out" : "amin");
-  SI_CHECK(out != spec, SPECINV_EINVAL, "specinv_spectral_envelope: out must not alias spec");
-  SI_CHECK(batch >= 1 && n_frames >= 1, SPECINV_EINVAL, "specinv_spectral_envelope: batch and n_frames must be >= 1, got %lld and %d",
-           (long long)batch, n_frames);
-  SI_CHECK(n_iter >= 0 && n_iter <= kEnvMaxIter, SPECINV_EINVAL, "specinv_spectral_envelope: n_iter must be in 0 ... %d, got %d",
-           kEnvMaxIter, n_iter);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_spectral_envelope: float32 only");
-  SI_CHECK(n_freq == 129 || n_freq == 257 || n_freq == 513 || n_freq == 1025, SPECINV_EUNSUPPORTED,
-           "specinv_spectral_envelope: n_freq must be 129, 257, 513 or 1025 (n_fft 256, 512, 1024 or 2048), got %d", n_freq);
-  SI_CHECK(order >= 0 && order <= n_freq - 1, SPECINV_EINVAL, "specinv_spectral_envelope: order must be in 0 ... %d, got %d",
-           n_freq - 1, order);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  return envelope_launch((const float*)spec, (float*)out, (const float*)amin, batch, n_freq, n_frames, order, n_iter, out_log != 0,
-                         is_complex != 0, frame_major != 0, static_cast<hipStream_t>(hip_stream));
-}
-int specinv_yin(const void* x, void* period_out, void* aper_out, void* tau_out, void* cmnd_out, int64_t batch, int64_t length,
-                int32_t frame, int32_t hop, int32_t center, int32_t tau_min, int32_t tau_max, double threshold, int32_t dtype,
-                int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(x && period_out && aper_out, SPECINV_EINVAL, "specinv_yin: NULL %s", !x ? "x" : !period_out ? "period_out" : "aper_out");
-  {
-    const void* p[5] = {x, period_out, aper_out, tau_out, cmnd_out};
-    static const char* const names[5] = {"x", "period_out", "aper_out", "tau_out", "cmnd_out"};
-    for (int i = 1; i < 5; ++i)
-      for (int j = 0; j < i; ++j)
-        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_yin: %s must not alias %s", names[i], names[j]);
-  }
-  SI_CHECK(batch >= 1, SPECINV_EINVAL, "specinv_yin: batch must be >= 1, got %lld", (long long)batch);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_yin: float32 only");
-  SI_CHECK(frame == 256 || frame == 512 || frame == 1024 || frame == 2048, SPECINV_EUNSUPPORTED,
-           "specinv_yin: frame must be 256, 512, 1024 or 2048, got %d", frame);
-  SI_CHECK(hop >= 1 && hop <= frame, SPECINV_EINVAL, "specinv_yin: hop must be in 1 ... %d, got %d", frame, hop);
-  SI_CHECK(length >= (center ? 1 : frame), SPECINV_EINVAL, "specinv_yin: a length of %lld gives no frame (center %d, frame %d)",
-           (long long)length, center, frame);
-  SI_CHECK(tau_min >= 1 && tau_max <= frame / 2 - 1 && tau_min < tau_max, SPECINV_EINVAL,
-           "specinv_yin: tau_min, tau_max must satisfy 1 <= tau_min < tau_max <= %d, got %d, %d", frame / 2 - 1, tau_min, tau_max);
-  SI_CHECK(std::isfinite(threshold) && threshold > 0, SPECINV_EINVAL, "specinv_yin: threshold must be finite and > 0, got %g", threshold);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  return yin_launch((const float*)x, (float*)period_out, (float*)aper_out, (int32_t*)tau_out, (float*)cmnd_out, batch, length, frame,
-                    hop, center != 0, tau_min, tau_max, threshold, static_cast<hipStream_t>(hip_stream));
-}
-int specinv_pyin_obs(const void* cmnd, const void* tables, void* obs_out, void* vprob_out, int64_t frames, int32_t frame,
-                     int32_t tau_min, int32_t tau_max, int32_t n_thresholds, int32_t n_ranks, int32_t n_bins, int32_t bins_per_semitone,
-                     double sample_rate, double fmin, double no_trough_prob, int32_t dtype, int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(cmnd && tables && obs_out && vprob_out, SPECINV_EINVAL, "specinv_pyin_obs: NULL %s",
-           !cmnd ? "cmnd" : !tables ? "tables" : !obs_out ? "obs_out" : "vprob_out");
-  SI_CHECK(obs_out != cmnd && vprob_out != cmnd && obs_out != tables && vprob_out != tables && obs_out != vprob_out, SPECINV_EINVAL,
-           "specinv_pyin_obs: an output must not alias an input or the other output");
-  SI_CHECK(frames >= 1, SPECINV_EINVAL, "specinv_pyin_obs: frames must be >= 1, got %lld", (long long)frames);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_pyin_obs: float32 only");
-  SI_CHECK(frame == 256 || frame == 512 || frame == 1024 || frame == 2048, SPECINV_EUNSUPPORTED,
-           "specinv_pyin_obs: frame must be 256, 512, 1024 or 2048, got %d", frame);
-  SI_CHECK(n_bins >= 1 && n_bins <= kPyinMaxBins, SPECINV_EUNSUPPORTED, "specinv_pyin_obs: n_bins must be in 1 ... %d, got %d",
-           kPyinMaxBins, n_bins);
-  SI_CHECK(n_thresholds >= 1 && n_thresholds <= kPyinMaxThresholds, SPECINV_EUNSUPPORTED,
-           "specinv_pyin_obs: n_thresholds must be in 1 ... %d, got %d", kPyinMaxThresholds, n_thresholds);
-  SI_CHECK(tau_min >= 1 && tau_max <= frame / 2 - 1 && tau_min < tau_max, SPECINV_EINVAL,
-           "specinv_pyin_obs: tau_min, tau_max must satisfy 1 <= tau_min < tau_max <= %d, got %d, %d", frame / 2 - 1, tau_min, tau_max);
-  SI_CHECK(n_ranks >= (tau_max - tau_min) / 2 + 1, SPECINV_EINVAL,
-           "specinv_pyin_obs: n_ranks must cover the %d troughs the range can hold, got %d", (tau_max - tau_min) / 2 + 1, n_ranks);
-  SI_CHECK(bins_per_semitone >= 1, SPECINV_EINVAL, "specinv_pyin_obs: bins_per_semitone must be >= 1, got %d", bins_per_semitone);
-  SI_CHECK(std::isfinite(sample_rate) && sample_rate > 0 && std::isfinite(fmin) && fmin > 0, SPECINV_EINVAL,
-           "specinv_pyin_obs: sample_rate and fmin must be finite and > 0, got %g and %g", sample_rate, fmin);
-  SI_CHECK(no_trough_prob >= 0 && no_trough_prob <= 1, SPECINV_EINVAL, "specinv_pyin_obs: no_trough_prob must be in 0 ... 1, got %g",
-           no_trough_prob);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  return pyin_obs_launch((const float*)cmnd, (const double*)tables, (float*)obs_out, (float*)vprob_out, frames, frame, tau_min, tau_max,
-                         n_thresholds, n_ranks, n_bins, bins_per_semitone, sample_rate, fmin, no_trough_prob,
-                         static_cast<hipStream_t>(hip_stream));
-}
-int specinv_pyin_viterbi(const void* obs, const void* vprob, const void* tables, void* backptr, void* states_out, void* ticks_out,
-                         int64_t batch, int64_t n_frames, int32_t n_bins, int32_t half_width, double switch_prob, int32_t dtype,
-                         int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(obs && vprob && tables && backptr && states_out, SPECINV_EINVAL, "specinv_pyin_viterbi: NULL %s",
-           !obs ? "obs" : !vprob ? "vprob" : !tables ? "tables" : !backptr ? "backptr" : "states_out");
-  {
-    const void* p[6] = {obs, vprob, tables, backptr, states_out, ticks_out};
-    static const char* const names[6] = {"obs", "vprob", "tables", "backptr", "states_out", "ticks_out"};
-    for (int i = 3; i < 6; ++i)
-      for (int j = 0; j < i; ++j)
-        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_pyin_viterbi: %s must not alias %s", names[i], names[j]);
-  }
-  SI_CHECK(batch >= 1 && n_frames >= 1, SPECINV_EINVAL, "specinv_pyin_viterbi: batch and n_frames must be >= 1, got %lld and %lld",
-           (long long)batch, (long long)n_frames);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_pyin_viterbi: float32 observations only");
-  SI_CHECK(n_bins >= 1 && n_bins <= kPyinMaxBins, SPECINV_EUNSUPPORTED, "specinv_pyin_viterbi: n_bins must be in 1 ... %d, got %d",
-           kPyinMaxBins, n_bins);
-  SI_CHECK(half_width >= 0 && half_width <= kPyinMaxHalf, SPECINV_EUNSUPPORTED,
-           "specinv_pyin_viterbi: half_width must be in 0 ... %d (a band of at most %d bins), got %d", kPyinMaxHalf,
-           2 * kPyinMaxHalf + 1, half_width);
-  SI_CHECK(switch_prob > 0 && switch_prob < 1, SPECINV_EINVAL, "specinv_pyin_viterbi: switch_prob must be in (0, 1), got %g",
-           switch_prob);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  return pyin_viterbi_launch((const float*)obs, (const float*)vprob, (const double*)tables, (int16_t*)backptr, (int32_t*)states_out,
-                             (int64_t*)ticks_out, batch, n_frames, n_bins, half_width, switch_prob,
-                             static_cast<hipStream_t>(hip_stream));
-}
-int specinv_enhance(const void* spec, const void* noise, const void* state_in, void* noise_out, void* spp_out, void* gain_out,
-                    void* snr_out, void* enhanced_out, void* state_out, int64_t batch, int64_t n_freq, int64_t n_frames,
-                    int32_t init_frames, int32_t noise_mode, int32_t rule, double alpha_pow, double alpha_spp, double prior_snr,
-                    double alpha, double xi_min, double gain_min, int32_t is_complex, int32_t frame_major, int32_t dtype,
-                    int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec, SPECINV_EINVAL, "specinv_enhance: NULL spec");
-  SI_CHECK(noise_out || spp_out || gain_out || snr_out || enhanced_out || state_out, SPECINV_EINVAL,
-           "specinv_enhance: every output is NULL");
-  SI_CHECK(noise_mode == SPECINV_ENHANCE_TRACK || noise_mode == SPECINV_ENHANCE_NOISE_FULL || noise_mode == SPECINV_ENHANCE_NOISE_PROFILE,
-           SPECINV_EINVAL, "specinv_enhance: noise_mode must be SPECINV_ENHANCE_TRACK, _NOISE_FULL or _NOISE_PROFILE, got %d", noise_mode);
-  SI_CHECK((noise_mode == SPECINV_ENHANCE_TRACK) == (noise == nullptr), SPECINV_EINVAL,
-           "specinv_enhance: noise must be NULL with SPECINV_ENHANCE_TRACK and given otherwise");
-  SI_CHECK(noise == nullptr || (noise_out == nullptr && spp_out == nullptr), SPECINV_EINVAL,
-           "specinv_enhance: with noise given the tracker does not run: noise_out and spp_out must be NULL");
-  {
-    const void* p[9] = {spec, noise, state_in, noise_out, spp_out, gain_out, snr_out, enhanced_out, state_out};
-    static const char* const names[9] = {"spec",     "noise",   "state_in",     "noise_out", "spp_out",
-                                         "gain_out", "snr_out", "enhanced_out", "state_out"};
-    for (int i = 1; i < 9; ++i)
-      for (int j = 0; j < i; ++j)
-        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_enhance: %s must not alias %s", names[i], names[j]);
-  }
-  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
-           "specinv_enhance: batch, n_freq and n_frames must be >= 1, got %lld, %lld and %lld", (long long)batch, (long long)n_freq,
-           (long long)n_frames);
-  SI_CHECK(batch <= (INT64_MAX >> 5) / n_freq / n_frames, SPECINV_EINVAL, "specinv_enhance: %lld x %lld x %lld elements are too many",
-           (long long)batch, (long long)n_freq, (long long)n_frames);
-  SI_CHECK(init_frames >= 1, SPECINV_EINVAL, "specinv_enhance: init_frames must be >= 1, got %d", init_frames);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(rule == SPECINV_ENHANCE_WIENER || rule == SPECINV_ENHANCE_LSA, SPECINV_EINVAL,
-           "specinv_enhance: rule must be SPECINV_ENHANCE_WIENER or SPECINV_ENHANCE_LSA, got %d", rule);
-  SI_CHECK(alpha_pow >= 0 && alpha_pow <= 1 && alpha_spp >= 0 && alpha_spp <= 1 && alpha >= 0 && alpha <= 1, SPECINV_EINVAL,
-           "specinv_enhance: alpha_pow, alpha_spp and alpha must be in 0 ... 1, got %g, %g and %g", alpha_pow, alpha_spp, alpha);
-  SI_CHECK(std::isfinite(prior_snr) && prior_snr > 0 && std::isfinite(xi_min) && xi_min > 0, SPECINV_EINVAL,
-           "specinv_enhance: prior_snr and xi_min must be finite and > 0, got %g and %g", prior_snr, xi_min);
-  SI_CHECK(gain_min > 0 && gain_min <= 1, SPECINV_EINVAL, "specinv_enhance: gain_min must be in (0, 1], got %g", gain_min);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  EnhArgs a;
-  a.spec = spec;
-  a.noise_in = noise;
-  a.state_in = (const double*)state_in;
-  a.noise_out = noise_out;
-  a.spp_out = spp_out;
-  a.gain_out = gain_out;
-  a.snr_out = snr_out;
-  a.enh_out = enhanced_out;
-  a.state_out = (double*)state_out;
-  a.batch = batch;
-  a.n_freq = n_freq;
-  a.n_frames = n_frames;
-  a.init_frames = init_frames;
-  a.noise_mode = noise_mode;
-  a.a_pow = alpha_pow;
-  a.a_spp = alpha_spp;
-  a.xi1p = 1.0 + prior_snr;
-  a.c = prior_snr / (1.0 + prior_snr);
-  a.alpha = alpha;
-  a.xi_min = xi_min;
-  a.g_min = gain_min;
-  return enhance_launch(a, dtype == SPECINV_F64, is_complex != 0, frame_major != 0, rule, static_cast<hipStream_t>(hip_stream));
-}
-int specinv_wpe(const void* spec, const void* power, const void* filt_in, void* out, void* filt_out, void* lam, void* scratch,
-                int64_t batch, int32_t channels, int64_t n_freq, int64_t n_frames, int32_t taps, int64_t delay, int32_t n_iter,
-                int64_t psd_context, double eps, double diag_load, int32_t dtype, int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec && out, SPECINV_EINVAL, "specinv_wpe: NULL spec or out");
-  SI_CHECK(filt_in == nullptr || (power == nullptr && filt_out == nullptr && lam == nullptr), SPECINV_EINVAL,
-           "specinv_wpe: with filt_in given nothing is estimated: power, filt_out and lam must be NULL");
-  SI_CHECK(filt_in != nullptr || lam != nullptr, SPECINV_EINVAL, "specinv_wpe: lam is NULL (it is the estimate's work array as well)");
-  SI_CHECK(filt_in != nullptr || psd_context <= 0 || scratch != nullptr, SPECINV_EINVAL,
-           "specinv_wpe: psd_context > 0 needs the scratch array");
-  {
-    const void* p[7] = {spec, power, filt_in, out, filt_out, lam, scratch};
-    static const char* const names[7] = {"spec", "power", "filt_in", "out", "filt_out", "lam", "scratch"};
-    for (int i = 3; i < 7; ++i)
-      for (int j = 0; j < i; ++j)
-        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_wpe: %s must not alias %s", names[i], names[j]);
-  }
-  SI_CHECK(batch >= 1 && channels >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
-           "specinv_wpe: batch, channels, n_freq and n_frames must be >= 1, got %lld, %d, %lld and %lld", (long long)batch, channels,
-           (long long)n_freq, (long long)n_frames);
-  SI_CHECK(batch <= (INT64_MAX >> 12) / n_freq / n_frames, SPECINV_EINVAL, "specinv_wpe: %lld x %lld x %lld elements a channel are too many",
-           (long long)batch, (long long)n_freq, (long long)n_frames);
-  SI_CHECK(taps >= 1, SPECINV_EINVAL, "specinv_wpe: taps must be >= 1, got %d", taps);
-  SI_CHECK(delay >= 1, SPECINV_EINVAL, "specinv_wpe: delay must be >= 1 (at 0 the filter predicts a frame from itself), got %lld",
-           (long long)delay);
-  SI_CHECK(n_iter >= 0 && psd_context >= 0, SPECINV_EINVAL, "specinv_wpe: n_iter and psd_context must be >= 0, got %d and %lld", n_iter,
-           (long long)psd_context);
-  SI_CHECK(eps >= 0 && std::isfinite(eps) && diag_load >= 0 && std::isfinite(diag_load), SPECINV_EINVAL,
-           "specinv_wpe: eps and diag_load must be finite and >= 0, got %g and %g", eps, diag_load);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(channels <= kWpeMaxD && taps <= kWpeMaxD && channels * taps <= kWpeMaxD, SPECINV_EUNSUPPORTED,
-           "specinv_wpe: channels x taps must be <= %d, got %d x %d", kWpeMaxD, channels, taps);
-  SI_CHECK(n_iter <= kWpeMaxIter && psd_context <= kWpeMaxContext, SPECINV_EUNSUPPORTED,
-           "specinv_wpe: n_iter must be <= %d and psd_context <= %d, got %d and %lld", kWpeMaxIter, kWpeMaxContext, n_iter,
-           (long long)psd_context);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  WpeArgs a;
-  a.spec = spec;
-  a.power = (const double*)power;
-  a.filt_in = filt_in;
-  a.out = out;
-  a.filt_out = filt_out;
-  a.lam = (double*)lam;
-  a.qbuf = (double*)scratch;
-  a.batch = batch;
-  a.n_freq = n_freq;
-  a.n_frames = n_frames;
-  a.delay = delay;
-  a.ctx = psd_context < n_frames ? psd_context : n_frames;     // (a wider context holds the same frames)
-  a.channels = channels;
-  a.taps = taps;
-  a.n_iter = n_iter;
-  a.eps = eps;
-  a.diag_load = diag_load;
-  return wpe_launch(a, dtype == SPECINV_F64, static_cast<hipStream_t>(hip_stream));
-}
-int specinv_beamform(const void* spec, const void* mask_target, const void* mask_noise, const void* weights_in, void* out,
-                     void* weights_out, void* scm_target, void* scm_noise, int64_t batch, int32_t channels, int64_t n_freq,
-                     int64_t n_frames, int32_t solution, int32_t ref_channel, int32_t n_power_iter, double diag_load, double mu,
-                     int32_t dtype, int32_t device, void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec, SPECINV_EINVAL, "specinv_beamform: NULL spec");
-  SI_CHECK(weights_in == nullptr || (mask_target == nullptr && mask_noise == nullptr && weights_out == nullptr && scm_target == nullptr &&
-                                     scm_noise == nullptr && out != nullptr),
-           SPECINV_EINVAL,
-           "specinv_beamform: with weights_in given nothing is estimated: out is needed, the masks, weights_out and the covariances "
-           "must be NULL");
-  SI_CHECK(weights_in != nullptr || out != nullptr || weights_out != nullptr || scm_target != nullptr || scm_noise != nullptr, SPECINV_EINVAL,
-           "specinv_beamform: no result is asked for");
-  SI_CHECK(weights_in != nullptr || mask_target != nullptr || (out == nullptr && weights_out == nullptr), SPECINV_EINVAL,
-           "specinv_beamform: weights need mask_target");
-  {
-    const void* p[8] = {spec, mask_target, mask_noise, weights_in, out, weights_out, scm_target, scm_noise};
-    static const char* const names[8] = {"spec", "mask_target", "mask_noise", "weights_in", "out", "weights_out", "scm_target", "scm_noise"};
-    for (int i = 4; i < 8; ++i)
-      for (int j = 0; j < i; ++j)
-        SI_CHECK(p[i] == nullptr || p[i] != p[j], SPECINV_EINVAL, "specinv_beamform: %s must not alias %s", names[i], names[j]);
-  }
-  SI_CHECK(batch >= 1 && channels >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
-           "specinv_beamform: batch, channels, n_freq and n_frames must be >= 1, got %lld, %d, %lld and %lld", (long long)batch, channels,
-           (long long)n_freq, (long long)n_frames);
-  SI_CHECK(batch <= (INT64_MAX >> 12) / n_freq / n_frames, SPECINV_EINVAL,
-           "specinv_beamform: %lld x %lld x %lld elements a channel are too many", (long long)batch, (long long)n_freq, (long long)n_frames);
-  SI_CHECK(solution == SPECINV_BEAMFORM_SOUDEN || solution == SPECINV_BEAMFORM_RTF_POWER || solution == SPECINV_BEAMFORM_MWF, SPECINV_EINVAL,
-           "specinv_beamform: unknown solution %d", solution);
-  SI_CHECK(ref_channel >= 0 && ref_channel < channels, SPECINV_EINVAL, "specinv_beamform: ref_channel must be in [0, %d), got %d", channels,
-           ref_channel);
-  SI_CHECK(n_power_iter >= 1, SPECINV_EINVAL, "specinv_beamform: n_power_iter must be >= 1, got %d", n_power_iter);
-  SI_CHECK(diag_load >= 0 && std::isfinite(diag_load) && mu >= 0 && std::isfinite(mu), SPECINV_EINVAL,
-           "specinv_beamform: diag_load and mu must be finite and >= 0, got %g and %g", diag_load, mu);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(channels <= kBfMaxChannels, SPECINV_EUNSUPPORTED, "specinv_beamform: channels must be <= %d, got %d", kBfMaxChannels, channels);
-  SI_CHECK(n_power_iter <= kBfMaxPowerIter, SPECINV_EUNSUPPORTED, "specinv_beamform: n_power_iter must be <= %d, got %d", kBfMaxPowerIter,
-           n_power_iter);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  BfArgs a;
-  a.spec = spec;
-  a.mask_t = (const double*)mask_target;
-  a.mask_n = (const double*)mask_noise;
-  a.w_in = weights_in;
-  a.out = out;
-  a.w_out = weights_out;
-  a.scm_t = scm_target;
-  a.scm_n = scm_noise;
-  a.batch = batch;
-  a.n_freq = n_freq;
-  a.n_frames = n_frames;
-  a.channels = channels;
-  a.solution = solution;
-  a.ref = ref_channel;
-  a.n_power_iter = n_power_iter;
-  a.diag_load = diag_load;
-  a.mu = mu;
-  return beamform_launch(a, dtype == SPECINV_F64, static_cast<hipStream_t>(hip_stream));
-}
-int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch, int64_t n_in,
-                  int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype, int32_t device,
-                  void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(x && centres && window && lags && y, SPECINV_EINVAL, "specinv_wsola: NULL %s",
-           !x ? "x" : !centres ? "centres" : !window ? "window" : !lags ? "lags" : "y");
-  SI_CHECK(y != x, SPECINV_EINVAL, "specinv_wsola: y must not alias x");
-  SI_CHECK(batch >= 1 && n_in >= 1 && n_out >= 1, SPECINV_EINVAL,
-           "specinv_wsola: batch, n_in and n_out must be >= 1, got %lld, %lld and %lld", (long long)batch, (long long)n_in,
-           (long long)n_out);
-  SI_CHECK(frame >= 2 && frame <= kWsolaMaxFrame && !(frame & 1), SPECINV_EINVAL, "specinv_wsola: frame must be even in 2 ... %d, got %d",
-           kWsolaMaxFrame, frame);
-  SI_CHECK(hop >= 1 && hop <= frame, SPECINV_EINVAL, "specinv_wsola: hop must be in 1 ... frame = %d, got %d", frame, hop);
-  SI_CHECK(tol >= 0 && tol <= kWsolaMaxTol, SPECINV_EINVAL, "specinv_wsola: tol must be in 0 ... %d, got %d", kWsolaMaxTol, tol);
-  const __int128 want = ((__int128)n_out - 1 + frame / 2) / hop + 1;
-  SI_CHECK((__int128)n_frames == want, SPECINV_EINVAL, "specinv_wsola: n_frames is %d, %lld outputs at frame %d and hop %d take %lld",
-           n_frames, (long long)n_out, frame, hop, (long long)want);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (dtype == SPECINV_F32)
-    return wsola_launch<float>((const float*)x, centres, (const float*)window, lags, (float*)y, batch, n_in, n_out, n_frames, frame,
-                               hop, tol, stream);
-  return wsola_launch<double>((const double*)x, centres, (const double*)window, lags, (double*)y, batch, n_in, n_out, n_frames,
-                              frame, hop, tol, stream);
-}
-int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
-                 int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
-                 void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(mag && spec_out, SPECINV_EINVAL, "specinv_pghi: NULL %s", !mag ? "mag" : "spec_out");
-  SI_CHECK(spec_out != mag, SPECINV_EINVAL, "specinv_pghi: spec_out must not alias mag");
-  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
-           "specinv_pghi: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
-  SI_CHECK(n_fft >= 2 && !(n_fft & 1) && n_freq == n_fft / 2 + 1, SPECINV_EINVAL,
-           "specinv_pghi: n_fft must be even and n_freq = n_fft / 2 + 1, got n_fft %d and n_freq %d", n_fft, n_freq);
-  SI_CHECK(hop >= 1, SPECINV_EINVAL, "specinv_pghi: hop must be >= 1, got %d", hop);
-  SI_CHECK(gamma > 0 && gamma <= 1.7976931348623157e308, SPECINV_EINVAL, "specinv_pghi: gamma must be finite and > 0, got %g", gamma);
-  SI_CHECK(tol > 0 && tol < 1, SPECINV_EINVAL, "specinv_pghi: tol must be in (0, 1), got %g", tol);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(n_fft <= kPghiMaxFft, SPECINV_EUNSUPPORTED, "specinv_pghi: n_fft %d is beyond %d, where a frame's state fills the LDS",
-           n_fft, kPghiMaxFft);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (dtype == SPECINV_F32)
-    return pghi_launch<float>((const float*)mag, (cplx<float>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft, hop,
-                              gamma, tol, stream);
-  return pghi_launch<double>((const double*)mag, (cplx<double>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft,
-                             hop, gamma, tol, stream);
-}
-int specinv_pvoc_pghi(const void* spec_in, void* spec_out, int8_t* parents_out, int64_t batch, int32_t n_freq, int32_t n_frames_in,
-                      int32_t n_frames_out, int32_t n_fft, int32_t hop, double rate, double tol, int32_t dtype, int32_t device,
-                      void* hip_stream) {
-  // (the argument errors before the device is touched, in the header's order)
-  SI_CHECK(spec_in && spec_out, SPECINV_EINVAL, "specinv_pvoc_pghi: NULL %s", !spec_in ? "spec_in" : "spec_out");
-  SI_CHECK(spec_out != spec_in, SPECINV_EINVAL, "specinv_pvoc_pghi: spec_out must not alias spec_in");
-  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames_in >= 1 && n_frames_out >= 1 && n_fft >= 1, SPECINV_EINVAL,
-           "specinv_pvoc_pghi: batch, n_freq, n_frames_in, n_frames_out and n_fft must be >= 1, got %lld, %d, %d, %d and %d",
-           (long long)batch, n_freq, n_frames_in, n_frames_out, n_fft);
-  SI_CHECK(n_freq == n_fft / 2 + 1, SPECINV_EINVAL,
-           "specinv_pvoc_pghi: one-sided spectra only, n_freq = n_fft / 2 + 1; got n_fft %d and n_freq %d", n_fft, n_freq);
-  SI_CHECK(hop >= 1, SPECINV_EINVAL, "specinv_pvoc_pghi: hop must be >= 1, got %d", hop);
-  SI_CHECK(rate > 0 && std::isfinite(rate), SPECINV_EINVAL, "specinv_pvoc_pghi: rate must be finite and > 0, got %g", rate);
-  const int64_t want = pvoc_stretched_frames(n_frames_in, rate);
-  SI_CHECK(want == (int64_t)n_frames_out, SPECINV_EINVAL, "specinv_pvoc_pghi: n_frames_out is %d, %d frames at rate %g stretch to %lld",
-           n_frames_out, n_frames_in, rate, (long long)want);
-  SI_CHECK(tol > 0 && tol < 1, SPECINV_EINVAL, "specinv_pvoc_pghi: tol must be in (0, 1), got %g", tol);
-  SI_CHECK(dtype == SPECINV_F32 || dtype == SPECINV_F64, SPECINV_EINVAL, "bad dtype %d", dtype);
-  SI_CHECK(n_freq <= kPghiMaxFreq, SPECINV_EUNSUPPORTED, "specinv_pvoc_pghi: n_freq %d is beyond %d, the bins a workgroup holds", n_freq,
-           kPghiMaxFreq);
-  DeviceGuard guard_;
-  SI_HIP(guard_.enter(device));
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (dtype == SPECINV_F32)
-    return pvoc_pghi_launch<float>((const cplx<float>*)spec_in, (cplx<float>*)spec_out, parents_out, batch, n_freq, n_frames_in,
-                                   n_frames_out, n_fft, hop, rate, tol, stream);
-  return pvoc_pghi_launch<double>((const cplx<double>*)spec_in, (cplx<double>*)spec_out, parents_out, batch, n_freq, n_frames_in,
-                                  n_frames_out, n_fft, hop, rate, tol, stream);
 }
 int specinv_cwf_run(specinv_plan* plan, const void* mix, const void* var_s, const void* var_n, double gamma, int relative, double floor,
                     int n_iter, int eva_iter, double tol, void* S_out, void* N_out, double* residual_out_host, int* iters_out) {

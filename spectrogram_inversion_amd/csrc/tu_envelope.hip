@@ -1,8 +1,10 @@
-// k_spectral_envelope (kernels_envelope.h) and its launch.
+// specinv_spectral_envelope: the entry point, and the launch of k_spectral_envelope (kernels_envelope.h).
+#include "entry.h"
 #include "kernels_envelope.h"
 
 namespace specinv {
 
+// Items and tiles are one flattened grid, in as many launches as 2^22 workgroups each take.
 template <int R, bool CPLX>
 static int envelope_launch_r(const EnvArgs& a, int64_t blocks, hipStream_t stream) {
   using E = EnvGeo<R>;
@@ -19,16 +21,32 @@ static int envelope_launch_r(const EnvArgs& a, int64_t blocks, hipStream_t strea
   return SPECINV_OK;
 }
 
-int envelope_launch(const float* spec, float* out, const float* amin, int64_t batch, int n_freq, int n_frames, int order, int n_iter,
-                    bool out_log, bool is_complex, bool frame_major, hipStream_t stream) {
-  const int n_fft = 2 * (n_freq - 1), R = n_fft / 64;
-  SI_CHECK(spec != nullptr && out != nullptr && amin != nullptr && batch >= 1 && n_frames >= 1 && n_freq == 32 * R + 1 &&
-               (R == 4 || R == 8 || R == 16 || R == 32) && order >= 0 && order <= n_fft / 2 && n_iter >= 0 && n_iter <= kEnvMaxIter,
-           SPECINV_EINVAL, "spectral_envelope: bad arguments");
+}  // namespace specinv
+
+using namespace specinv;
+
+extern "C" int specinv_spectral_envelope(const void* spec, void* out, const void* amin, int64_t batch, int32_t n_freq, int32_t n_frames,
+                                         int32_t order, int32_t n_iter, int32_t out_log, int32_t is_complex, int32_t frame_major,
+                                         int32_t dtype, int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec && out && amin, SPECINV_EINVAL, "specinv_spectral_envelope: NULL %s", !spec ? "spec" : !out ? "out" : "amin");
+  SI_CHECK(out != spec, SPECINV_EINVAL, "specinv_spectral_envelope: out must not alias spec");
+  SI_CHECK(batch >= 1 && n_frames >= 1, SPECINV_EINVAL, "specinv_spectral_envelope: batch and n_frames must be >= 1, got %lld and %d",
+           (long long)batch, n_frames);
+  SI_CHECK(n_iter >= 0 && n_iter <= kEnvMaxIter, SPECINV_EINVAL, "specinv_spectral_envelope: n_iter must be in 0 ... %d, got %d",
+           kEnvMaxIter, n_iter);
+  SI_CHECK_DTYPE(dtype);
+  SI_CHECK(dtype == SPECINV_F32, SPECINV_EUNSUPPORTED, "specinv_spectral_envelope: float32 only");
+  SI_CHECK(n_freq == 129 || n_freq == 257 || n_freq == 513 || n_freq == 1025, SPECINV_EUNSUPPORTED,
+           "specinv_spectral_envelope: n_freq must be 129, 257, 513 or 1025 (n_fft 256, 512, 1024 or 2048), got %d", n_freq);
+  SI_CHECK(order >= 0 && order <= n_freq - 1, SPECINV_EINVAL, "specinv_spectral_envelope: order must be in 0 ... %d, got %d",
+           n_freq - 1, order);
+  SI_ENTER_DEVICE(device, hip_stream);
+  const int R = (n_freq - 1) / 32;           // n_fft / 64
   EnvArgs a;
-  a.spec = spec;
-  a.out = out;
-  a.amin = amin;
+  a.spec = (const float*)spec;
+  a.out = (float*)out;
+  a.amin = (const float*)amin;
   a.n_frames = n_frames;
   a.order = order;
   a.n_iter = n_iter;
@@ -51,5 +69,3 @@ int envelope_launch(const float* spec, float* out, const float* amin, int64_t ba
   }
 #undef SPECINV_ENV_CASE
 }
-
-}  // namespace specinv

@@ -1,14 +1,13 @@
-// k_hpss (kernels_hpss.h) and its launch.
+// specinv_hpss: the entry point, and the launch of k_hpss (kernels_hpss.h).
+#include "entry.h"
 #include "kernels_hpss.h"
 
 namespace specinv {
 
+// Batch and the two tile counts are one flattened grid, in as many launches as 2^22 workgroups each take.
 template <typename T>
-int hpss_launch(const T* spec, T* out_a, T* out_b, int64_t batch, int n_freq, int n_frames, int k_h, int k_p, double power,
-                double m_h, double m_p, int mode, bool is_complex, hipStream_t stream) {
-  SI_CHECK(spec != nullptr && out_a != nullptr && out_b != nullptr && batch >= 1 && n_freq >= 1 && n_frames >= 1 && k_h >= 1 &&
-               k_h <= kHpssMaxWin && (k_h & 1) && k_p >= 1 && k_p <= kHpssMaxWin && (k_p & 1) && power > 0 && m_h >= 1 && m_p >= 1,
-           SPECINV_EINVAL, "hpss: bad arguments");
+static int hpss_launch(const T* spec, T* out_a, T* out_b, int64_t batch, int n_freq, int n_frames, int k_h, int k_p, double power,
+                       double m_h, double m_p, int mode, bool is_complex, hipStream_t stream) {
   HpssArgs a;
   size_t lds = 0;
   a.tile_f = hpss_tile_rows(k_h, k_p, is_complex ? sizeof(double) : sizeof(T), &lds);
@@ -40,9 +39,35 @@ int hpss_launch(const T* spec, T* out_a, T* out_b, int64_t batch, int n_freq, in
   return SPECINV_OK;
 }
 
-template int hpss_launch<float>(const float*, float*, float*, int64_t, int, int, int, int, double, double, double, int, bool,
-                                hipStream_t);
-template int hpss_launch<double>(const double*, double*, double*, int64_t, int, int, int, int, double, double, double, int, bool,
-                                 hipStream_t);
-
 }  // namespace specinv
+
+using namespace specinv;
+
+extern "C" int specinv_hpss(const void* spec, void* out_a, void* out_b, int64_t batch, int32_t n_freq, int32_t n_frames,
+                            int32_t win_harm, int32_t win_perc, double power, double margin_harm, double margin_perc, int32_t out_mode,
+                            int32_t is_complex, int32_t dtype, int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(spec && out_a && out_b, SPECINV_EINVAL, "specinv_hpss: NULL %s", !spec ? "spec" : !out_a ? "out_a" : "out_b");
+  SI_CHECK(out_a != spec && out_b != spec && out_a != out_b, SPECINV_EINVAL, "specinv_hpss: %s",
+           out_a == out_b ? "out_b must not alias out_a" : "an output must not alias spec");
+  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
+           "specinv_hpss: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
+  SI_CHECK(win_harm >= 1 && win_harm <= kHpssMaxWin && (win_harm & 1), SPECINV_EINVAL,
+           "specinv_hpss: win_harm must be odd in 1 ... %d, got %d", kHpssMaxWin, win_harm);
+  SI_CHECK(win_perc >= 1 && win_perc <= kHpssMaxWin && (win_perc & 1), SPECINV_EINVAL,
+           "specinv_hpss: win_perc must be odd in 1 ... %d, got %d", kHpssMaxWin, win_perc);
+  SI_CHECK(power > 0, SPECINV_EINVAL, "specinv_hpss: power must be > 0 (inf included), got %g", power);
+  SI_CHECK(margin_harm >= 1 && std::isfinite(margin_harm), SPECINV_EINVAL, "specinv_hpss: margin_harm must be finite and >= 1, got %g",
+           margin_harm);
+  SI_CHECK(margin_perc >= 1 && std::isfinite(margin_perc), SPECINV_EINVAL, "specinv_hpss: margin_perc must be finite and >= 1, got %g",
+           margin_perc);
+  SI_CHECK(out_mode == SPECINV_HPSS_COMPONENTS || out_mode == SPECINV_HPSS_MASKS || out_mode == SPECINV_HPSS_MEDIANS, SPECINV_EINVAL,
+           "specinv_hpss: out_mode must be SPECINV_HPSS_COMPONENTS, _MASKS or _MEDIANS, got %d", out_mode);
+  SI_CHECK_DTYPE(dtype);
+  SI_ENTER_DEVICE(device, hip_stream);
+  if (dtype == SPECINV_F32)
+    return hpss_launch<float>((const float*)spec, (float*)out_a, (float*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
+                              margin_harm, margin_perc, out_mode, is_complex != 0, stream);
+  return hpss_launch<double>((const double*)spec, (double*)out_a, (double*)out_b, batch, n_freq, n_frames, win_harm, win_perc, power,
+                             margin_harm, margin_perc, out_mode, is_complex != 0, stream);
+}

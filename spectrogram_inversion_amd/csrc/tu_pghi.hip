@@ -1,4 +1,5 @@
-// k_pghi (kernels_pghi.h) and its launch.
+// specinv_pghi: the entry point, and the launch of k_pghi (kernels_pghi.h).
+#include "entry.h"
 #include "kernels_pghi.h"
 
 namespace specinv {
@@ -14,12 +15,10 @@ static int pghi_run(const T* mag, cplx<T>* out, double* phase_out, int8_t* paren
   return SPECINV_OK;
 }
 
+// One launch; the grid is min(batch, 2^16) workgroups.
 template <typename T>
-int pghi_launch(const T* mag, cplx<T>* out, double* phase_out, int8_t* parents_out, int64_t batch, int n_freq, int n_frames,
-                int n_fft, int hop, double gamma, double tol, hipStream_t stream) {
-  SI_CHECK(mag != nullptr && out != nullptr && batch >= 1 && n_frames >= 1 && n_fft >= 2 && !(n_fft & 1) && n_freq == n_fft / 2 + 1 &&
-               n_freq <= kPghiMaxFreq && hop >= 1 && gamma > 0 && tol > 0 && tol < 1,
-           SPECINV_EINVAL, "pghi: bad arguments");
+static int pghi_launch(const T* mag, cplx<T>* out, double* phase_out, int8_t* parents_out, int64_t batch, int n_freq, int n_frames,
+                       int n_fft, int hop, double gamma, double tol, hipStream_t stream) {
   PghiArgs a;
   a.batch = batch;
   a.n_freq = n_freq;
@@ -42,8 +41,30 @@ int pghi_launch(const T* mag, cplx<T>* out, double* phase_out, int8_t* parents_o
   return fail(SPECINV_EUNSUPPORTED, "pghi: %d bins are more than %d per lane", n_freq, kPghiMaxChunk);
 }
 
-template int pghi_launch<float>(const float*, cplx<float>*, double*, int8_t*, int64_t, int, int, int, int, double, double, hipStream_t);
-template int pghi_launch<double>(const double*, cplx<double>*, double*, int8_t*, int64_t, int, int, int, int, double, double,
-                                 hipStream_t);
-
 }  // namespace specinv
+
+using namespace specinv;
+
+extern "C" int specinv_pghi(const void* mag, void* spec_out, double* phase_out, int8_t* parents_out, int64_t batch, int32_t n_freq,
+                            int32_t n_frames, int32_t n_fft, int32_t hop, double gamma, double tol, int32_t dtype, int32_t device,
+                            void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(mag && spec_out, SPECINV_EINVAL, "specinv_pghi: NULL %s", !mag ? "mag" : "spec_out");
+  SI_CHECK(spec_out != mag, SPECINV_EINVAL, "specinv_pghi: spec_out must not alias mag");
+  SI_CHECK(batch >= 1 && n_freq >= 1 && n_frames >= 1, SPECINV_EINVAL,
+           "specinv_pghi: batch, n_freq and n_frames must be >= 1, got %lld, %d and %d", (long long)batch, n_freq, n_frames);
+  SI_CHECK(n_fft >= 2 && !(n_fft & 1) && n_freq == n_fft / 2 + 1, SPECINV_EINVAL,
+           "specinv_pghi: n_fft must be even and n_freq = n_fft / 2 + 1, got n_fft %d and n_freq %d", n_fft, n_freq);
+  SI_CHECK(hop >= 1, SPECINV_EINVAL, "specinv_pghi: hop must be >= 1, got %d", hop);
+  SI_CHECK(gamma > 0 && gamma <= 1.7976931348623157e308, SPECINV_EINVAL, "specinv_pghi: gamma must be finite and > 0, got %g", gamma);
+  SI_CHECK(tol > 0 && tol < 1, SPECINV_EINVAL, "specinv_pghi: tol must be in (0, 1), got %g", tol);
+  SI_CHECK_DTYPE(dtype);
+  SI_CHECK(n_fft <= kPghiMaxFft, SPECINV_EUNSUPPORTED, "specinv_pghi: n_fft %d is beyond %d, where a frame's state fills the LDS",
+           n_fft, kPghiMaxFft);
+  SI_ENTER_DEVICE(device, hip_stream);
+  if (dtype == SPECINV_F32)
+    return pghi_launch<float>((const float*)mag, (cplx<float>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft, hop,
+                              gamma, tol, stream);
+  return pghi_launch<double>((const double*)mag, (cplx<double>*)spec_out, phase_out, parents_out, batch, n_freq, n_frames, n_fft,
+                             hop, gamma, tol, stream);
+}

@@ -1,15 +1,14 @@
-// k_wsola_lags, k_wsola_ola (kernels_wsola.h) and their launch.
+// specinv_wsola: the entry point, and the launch of k_wsola_lags and k_wsola_ola (kernels_wsola.h).
+#include "entry.h"
 #include "kernels_wsola.h"
 
 namespace specinv {
 
+// lags is always written (zeros without a chain: tol 0 or one frame).  Batch is part of grid x, in as many launches as 2^22
+// workgroups each take.
 template <typename T>
-int wsola_launch(const T* x, const int64_t* centres, const T* window, int32_t* lags, T* y, int64_t batch, int64_t n_in,
-                 int64_t n_out, int n_frames, int frame, int hop, int tol, hipStream_t stream) {
-  SI_CHECK(x != nullptr && centres != nullptr && window != nullptr && lags != nullptr && y != nullptr && batch >= 1 && n_in >= 1 &&
-               n_out >= 1 && n_frames >= 1 && frame >= 2 && frame <= kWsolaMaxFrame && !(frame & 1) && hop >= 1 && hop <= frame &&
-               tol >= 0 && tol <= kWsolaMaxTol,
-           SPECINV_EINVAL, "wsola: bad arguments");
+static int wsola_launch(const T* x, const int64_t* centres, const T* window, int32_t* lags, T* y, int64_t batch, int64_t n_in,
+                        int64_t n_out, int n_frames, int frame, int hop, int tol, hipStream_t stream) {
   WsolaArgs a;
   a.n_in = n_in;
   a.n_out = n_out;
@@ -46,9 +45,32 @@ int wsola_launch(const T* x, const int64_t* centres, const T* window, int32_t* l
   return SPECINV_OK;
 }
 
-template int wsola_launch<float>(const float*, const int64_t*, const float*, int32_t*, float*, int64_t, int64_t, int64_t, int, int,
-                                 int, int, hipStream_t);
-template int wsola_launch<double>(const double*, const int64_t*, const double*, int32_t*, double*, int64_t, int64_t, int64_t, int,
-                                  int, int, int, hipStream_t);
-
 }  // namespace specinv
+
+using namespace specinv;
+
+extern "C" int specinv_wsola(const void* x, const int64_t* centres, const void* window, int32_t* lags, void* y, int64_t batch,
+                             int64_t n_in, int64_t n_out, int32_t n_frames, int32_t frame, int32_t hop, int32_t tol, int32_t dtype,
+                             int32_t device, void* hip_stream) {
+  // (the argument errors before the device is touched, in the header's order)
+  SI_CHECK(x && centres && window && lags && y, SPECINV_EINVAL, "specinv_wsola: NULL %s",
+           !x ? "x" : !centres ? "centres" : !window ? "window" : !lags ? "lags" : "y");
+  SI_CHECK(y != x, SPECINV_EINVAL, "specinv_wsola: y must not alias x");
+  SI_CHECK(batch >= 1 && n_in >= 1 && n_out >= 1, SPECINV_EINVAL,
+           "specinv_wsola: batch, n_in and n_out must be >= 1, got %lld, %lld and %lld", (long long)batch, (long long)n_in,
+           (long long)n_out);
+  SI_CHECK(frame >= 2 && frame <= kWsolaMaxFrame && !(frame & 1), SPECINV_EINVAL, "specinv_wsola: frame must be even in 2 ... %d, got %d",
+           kWsolaMaxFrame, frame);
+  SI_CHECK(hop >= 1 && hop <= frame, SPECINV_EINVAL, "specinv_wsola: hop must be in 1 ... frame = %d, got %d", frame, hop);
+  SI_CHECK(tol >= 0 && tol <= kWsolaMaxTol, SPECINV_EINVAL, "specinv_wsola: tol must be in 0 ... %d, got %d", kWsolaMaxTol, tol);
+  const __int128 want = ((__int128)n_out - 1 + frame / 2) / hop + 1;
+  SI_CHECK((__int128)n_frames == want, SPECINV_EINVAL, "specinv_wsola: n_frames is %d, %lld outputs at frame %d and hop %d take %lld",
+           n_frames, (long long)n_out, frame, hop, (long long)want);
+  SI_CHECK_DTYPE(dtype);
+  SI_ENTER_DEVICE(device, hip_stream);
+  if (dtype == SPECINV_F32)
+    return wsola_launch<float>((const float*)x, centres, (const float*)window, lags, (float*)y, batch, n_in, n_out, n_frames, frame,
+                               hop, tol, stream);
+  return wsola_launch<double>((const double*)x, centres, (const double*)window, lags, (double*)y, batch, n_in, n_out, n_frames,
+                              frame, hop, tol, stream);
+}

@@ -26,14 +26,12 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-import numbers
 
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import broadcasts_to, ingest, is_int, is_real
 from .plan import _RECOGNISED, require_gpu
 
 __all__ = ["wpe", "wpe_apply", "dereverb"]
@@ -47,13 +45,13 @@ _REAL = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
 
 
 def _int(v, name, lo):
-    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+    if not is_int(v) or v < lo:
         raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
     return v
 
 
 def _checked_delay(delay):
-    if isinstance(delay, bool) or not isinstance(delay, int):
+    if not is_int(delay):
         raise ValueError(f"delay must be an int >= 1, got {delay!r}")
     if delay < 1:
         raise ValueError(f"delay must be >= 1 (at 0 the filter predicts a frame from itself and the result is zero), got {delay!r}")
@@ -71,7 +69,7 @@ def _checked_params(taps, delay, n_iter, psd_context, eps, diag_load):
         raise NotImplementedError(f"psd_context must be <= {MAX_CONTEXT} (a frame's power is averaged over 2 psd_context + 1 reads), "
                                   f"got {psd_context}")
     for v, name in ((eps, "eps"), (diag_load, "diag_load")):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (v >= 0 and math.isfinite(v)):
+        if not is_real(v) or not (v >= 0 and math.isfinite(v)):
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     return taps, delay, n_iter, psd_context, float(eps), float(diag_load)
 
@@ -105,7 +103,6 @@ def _launch(spec, lead, channels, n_freq, n_frames, taps, delay, n_iter, ctx, ep
         return (spec.new_zeros(spec.shape), spec.new_zeros(g_shape, dtype=torch.complex128) if want_filter else None,
                 spec.new_zeros(lead + (n_freq, n_frames), dtype=torch.float64) if want_power else None)
     device = require_gpu(spec.device)
-    lib = _lib.load()
     s4 = ingest(spec.reshape((-1, channels, n_freq, n_frames)), device, spec.dtype)
     batch = s4.shape[0]
     out = torch.empty_like(s4)
@@ -120,12 +117,8 @@ def _launch(spec, lead, channels, n_freq, n_frames, taps, delay, n_iter, ctx, ep
             scratch = torch.empty_like(lam)
         if want_filter:
             g_out = torch.empty((batch, n_freq, d, channels), dtype=torch.complex128, device=device)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_wpe(ptr(s4), ptr(pw), ptr(g_in), ptr(out), ptr(g_out), ptr(lam), ptr(scratch), batch, channels, n_freq,
-                               n_frames, taps, delay, n_iter, ctx, eps, diag_load,
-                               _lib.F32 if spec.dtype == torch.complex64 else _lib.F64, stream.device.index,
-                               C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_wpe", (s4, pw, g_in, out, g_out, lam, scratch, batch, channels, n_freq, n_frames, taps, delay, n_iter, ctx,
+                                 eps, diag_load), spec.dtype != torch.complex64, device)
     back = lambda t, shape: t.reshape(shape).to(device=spec.device)       # noqa: E731
     return (back(out, spec.shape), back(g_out, g_shape) if want_filter else None,
             back(lam, lead + (n_freq, n_frames)) if want_power else None)
@@ -162,11 +155,7 @@ def wpe(spec, taps=10, delay=3, n_iter=3, psd_context=0, eps=1e-10, diag_load=1e
         if power.dtype not in _REAL:
             raise TypeError(f"power must be real (float16 / bfloat16 / float32 / float64), got dtype {power.dtype}")
         want = lead + (n_freq, n_frames)
-        try:
-            ok = torch.broadcast_shapes(tuple(power.shape), want) == want
-        except RuntimeError:
-            ok = False
-        if not ok:
+        if not broadcasts_to(power.shape, want):
             raise ValueError(f"power of shape {tuple(power.shape)} does not broadcast to {want}, spec's shape without the channel axis")
         if torch.is_grad_enabled() and power.requires_grad:
             raise NotImplementedError("wpe is not differentiable; detach the inputs")

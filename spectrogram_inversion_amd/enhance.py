@@ -47,14 +47,12 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-import numbers
 
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import broadcasts_to, ingest, is_int, is_real
 from .plan import _RECOGNISED, require_gpu
 
 __all__ = ["noise_psd", "spectral_gain", "denoise"]
@@ -69,15 +67,15 @@ _REAL = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
 
 
 def _unit(v, name):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0 <= v <= 1:
+    if not is_real(v) or not 0 <= v <= 1:
         raise ValueError(f"{name} must be a number in 0 ... 1, got {v!r}")
     return float(v)
 
 
 def _checked_tracker(init_frames, alpha_pow, alpha_spp, prior_snr_db):
-    if isinstance(init_frames, bool) or not isinstance(init_frames, int) or not 1 <= init_frames < 1 << 31:
+    if not is_int(init_frames) or not 1 <= init_frames < 1 << 31:
         raise ValueError(f"init_frames must be an int >= 1, got {init_frames!r}")
-    if isinstance(prior_snr_db, bool) or not isinstance(prior_snr_db, numbers.Real) or not -3000 <= prior_snr_db <= 3000:
+    if not is_real(prior_snr_db) or not -3000 <= prior_snr_db <= 3000:
         raise ValueError(f"prior_snr_db must be a number in -3000 ... 3000, got {prior_snr_db!r}")
     return init_frames, _unit(alpha_pow, "alpha_pow"), _unit(alpha_spp, "alpha_spp"), 10.0 ** (prior_snr_db / 10.0)
 
@@ -85,9 +83,9 @@ def _checked_tracker(init_frames, alpha_pow, alpha_spp, prior_snr_db):
 def _checked_gain(rule, alpha, xi_min_db, gain_floor_db):
     if rule not in _lib.ENHANCE_RULES:
         raise ValueError(f"rule must be 'wiener' or 'lsa', got {rule!r}")
-    if isinstance(xi_min_db, bool) or not isinstance(xi_min_db, numbers.Real) or not -3000 <= xi_min_db <= 3000:
+    if not is_real(xi_min_db) or not -3000 <= xi_min_db <= 3000:
         raise ValueError(f"xi_min_db must be a number in -3000 ... 3000, got {xi_min_db!r}")
-    if isinstance(gain_floor_db, bool) or not isinstance(gain_floor_db, numbers.Real) or not -6000 <= gain_floor_db <= 0:
+    if not is_real(gain_floor_db) or not -6000 <= gain_floor_db <= 0:
         raise ValueError(f"gain_floor_db must be a number in -6000 ... 0, got {gain_floor_db!r}")
     return _lib.ENHANCE_RULES[rule], _unit(alpha, "alpha"), 10.0 ** (xi_min_db / 10.0), 10.0 ** (gain_floor_db / 20.0)
 
@@ -123,11 +121,7 @@ def _checked_noise(noise, spec, what):
         raise TypeError("noise must be a torch.Tensor")
     if noise.dtype not in _REAL:
         raise TypeError(f"noise must be real (float16 / bfloat16 / float32 / float64), got dtype {noise.dtype}")
-    try:
-        ok = torch.broadcast_shapes(tuple(noise.shape), tuple(spec.shape)) == tuple(spec.shape)
-    except RuntimeError:
-        ok = False
-    if not ok:
+    if not broadcasts_to(noise.shape, spec.shape):
         raise ValueError(f"noise of shape {tuple(noise.shape)} does not broadcast to spec's {tuple(spec.shape)}")
     if torch.is_grad_enabled() and noise.requires_grad:
         raise NotImplementedError(f"{what} is not differentiable; detach the inputs")
@@ -146,7 +140,6 @@ def _run(spec, n_freq, n_frames, frame_major, noise, state, rule, tracker, gain,
             res["state"] = spec.new_zeros(lead + (n_freq, 3), dtype=torch.float64)
         return res
     device = require_gpu(spec.device)
-    lib = _lib.load()
     shape3 = (-1,) + tuple(spec.shape[-2:])
     in_dtype = (torch.complex64 if cdt == torch.float32 else torch.complex128) if cplx else cdt
     s3 = ingest(spec.reshape(shape3), device, in_dtype)
@@ -168,13 +161,9 @@ def _run(spec, n_freq, n_frames, frame_major, noise, state, rule, tracker, gain,
             continue                                               # (the tracker does not run: it is the input, below)
         else:
             outs[k] = torch.empty(s3.shape, dtype=in_dtype if k == "enhanced" else cdt, device=device)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_enhance(ptr(s3), ptr(nz), ptr(st_in), ptr(outs.get("noise")), ptr(outs.get("spp")), ptr(outs.get("gain")),
-                                   ptr(outs.get("snr")), ptr(outs.get("enhanced")), ptr(outs.get("state")), batch, n_freq, n_frames,
-                                   init_frames, mode, rule, a_pow, a_spp, xi1, alpha, xi_min, g_min, int(cplx), int(bool(frame_major)),
-                                   _lib.F32 if cdt == torch.float32 else _lib.F64, stream.device.index,
-                                   C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_enhance", (s3, nz, st_in, outs.get("noise"), outs.get("spp"), outs.get("gain"), outs.get("snr"),
+                                     outs.get("enhanced"), outs.get("state"), batch, n_freq, n_frames, init_frames, mode, rule, a_pow,
+                                     a_spp, xi1, alpha, xi_min, g_min, int(cplx), int(bool(frame_major))), cdt != torch.float32, device)
     res = {}
     for k in want:
         if k == "state":
@@ -256,9 +245,9 @@ def denoise(x, n_fft=None, rule="lsa", consistent=False, gamma=1.0, n_iter=30, a
         raise TypeError("x must be a torch.Tensor")
     _checked_gain(rule, alpha, xi_min_db, gain_floor_db)
     _checked_tracker(init_frames, alpha_pow, alpha_spp, prior_snr_db)
-    if isinstance(gamma, bool) or not isinstance(gamma, numbers.Real) or not (gamma > 0 and math.isfinite(gamma)):
+    if not is_real(gamma) or not (gamma > 0 and math.isfinite(gamma)):
         raise ValueError(f"gamma must be a finite number > 0, got {gamma!r}")
-    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+    if not is_int(n_iter) or n_iter < 0:
         raise ValueError(f"n_iter must be an int >= 0, got {n_iter!r}")
     if torch.is_grad_enabled() and x.requires_grad:
         raise NotImplementedError("denoise is not differentiable; detach the input")

@@ -25,7 +25,6 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import numbers
 
@@ -135,18 +134,15 @@ def spectral_envelope(spec, order, n_iter=16, floor=1e-6, log=False, frame_major
     if spec.numel() == 0:
         return spec.new_zeros(spec.shape, dtype=out_dtype)
     device = require_gpu(spec.device)
-    lib = _lib.load()
     s3 = ingest(spec.reshape((-1,) + tuple(spec.shape[-2:])), device, torch.complex64 if cplx else torch.float32)
     amin = (s3.abs().amax(dim=(1, 2)) * floor).to(torch.float32).contiguous()       # a one-off pass, not the hot path
     out = torch.empty(s3.shape, dtype=torch.float32, device=device)
-    stream = torch.cuda.current_stream(device)
     tile = 32 if n_fft <= 512 else 16 if n_fft == 1024 else 8                        # frames per workgroup (kernels_envelope.h)
     per_call = max(1, _MAX_BLOCKS // -(-n_frames // tile))                           # items whose workgroups fit one call
     for b0 in range(0, s3.shape[0], per_call):
         nb = min(per_call, s3.shape[0] - b0)
-        _lib.check(lib.specinv_spectral_envelope(s3[b0:].data_ptr(), out[b0:].data_ptr(), amin[b0:].data_ptr(), nb, n_freq, n_frames,
-                                                 order, n_iter, int(bool(log)), int(cplx), int(bool(frame_major)), _lib.F32,
-                                                 stream.device.index, C.c_void_p(stream.cuda_stream)))
+        _lib.call_op("specinv_spectral_envelope", (s3[b0:], out[b0:], amin[b0:], nb, n_freq, n_frames, order, n_iter, int(bool(log)),
+                                                   int(cplx), int(bool(frame_major))), False, device)
     return out.reshape(spec.shape).to(device=spec.device, dtype=out_dtype)
 
 

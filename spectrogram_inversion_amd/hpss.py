@@ -33,7 +33,6 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import numbers
 
@@ -109,17 +108,13 @@ def _run(spec, sizes, power, margins, mode):
     if spec.numel() == 0:
         return spec.new_zeros(spec.shape, dtype=out_dtype), spec.new_zeros(spec.shape, dtype=out_dtype)
     device = require_gpu(spec.device)
-    lib = _lib.load()
     work = (torch.complex64 if rdtype == torch.float32 else torch.complex128) if cplx else rdtype
     s3 = ingest(spec.reshape((-1,) + tuple(spec.shape[-2:])), device, work)
     out_work = work if out_cplx else rdtype
     out_a = torch.empty(s3.shape, dtype=out_work, device=device)
     out_b = torch.empty(s3.shape, dtype=out_work, device=device)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_hpss(s3.data_ptr(), out_a.data_ptr(), out_b.data_ptr(), s3.shape[0], s3.shape[1], s3.shape[2], sizes[0],
-                                sizes[1], power, margins[0], margins[1], mode, int(cplx),
-                                _lib.F32 if rdtype == torch.float32 else _lib.F64, stream.device.index,
-                                C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_hpss", (s3, out_a, out_b, s3.shape[0], s3.shape[1], s3.shape[2], sizes[0], sizes[1], power, margins[0],
+                                  margins[1], mode, int(cplx)), rdtype != torch.float32, device)
     return tuple(o.reshape(spec.shape).to(device=spec.device, dtype=out_dtype) for o in (out_a, out_b))
 
 

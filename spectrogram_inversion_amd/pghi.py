@@ -40,7 +40,6 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import numbers
 
@@ -125,16 +124,12 @@ def rtpghi(spec, gamma=None, tol=1e-6, return_phase=False, return_parents=False,
             res.append(spec.new_zeros((0,) + tuple(spec.shape[-2:]), dtype=torch.int8))
         return res[0] if len(res) == 1 else tuple(res)
     device = require_gpu(spec.device)
-    lib = _lib.load()
     s3 = ingest(spec.reshape(shape3), device, dtype)
     out = torch.empty(s3.shape, dtype=cdtype, device=device)
     phase = torch.empty(s3.shape, dtype=torch.float64, device=device) if return_phase else None
     parents = torch.empty(s3.shape, dtype=torch.int8, device=device) if return_parents else None
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_pghi(s3.data_ptr(), out.data_ptr(), phase.data_ptr() if return_phase else None,
-                                parents.data_ptr() if return_parents else None, s3.shape[0], s3.shape[1], s3.shape[2], args.n_fft,
-                                args.hop_length, gamma, float(tol), _lib.F32 if dtype == torch.float32 else _lib.F64,
-                                stream.device.index, C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_pghi", (s3, out, phase, parents, s3.shape[0], s3.shape[1], s3.shape[2], args.n_fft, args.hop_length, gamma,
+                                  float(tol)), dtype != torch.float32, device)
     res = [out.reshape(spec.shape).to(device=spec.device, dtype=out_dtype)]
     if return_phase:
         res.append(phase.to(spec.device))

@@ -65,15 +65,13 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import math
-import numbers
 
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import ingest, is_int as _is_int, is_real
 from .plan import require_gpu
 
 __all__ = ["yin", "yin_cmnd", "yin_frames", "pyin", "pyin_observations", "pyin_decode", "pyin_bins"]
@@ -84,12 +82,8 @@ _MAX_BLOCKS = 65535            # workgroups one call of the entry point is given
 _WAVES = 4                     # frames a workgroup takes (kernels_yin.h): an item is ceil(T / 4) workgroups
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def _is_real(v):
-    return isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
+    return is_real(v) and math.isfinite(v)
 
 
 def _checked_frame(frame_length, hop_length):
@@ -163,20 +157,16 @@ def _run(x, what, n, h, center, tau_min, tau_max, threshold, want_tau, want_cmnd
         return (period, period.clone(), torch.zeros(lead + (n_frames,), dtype=torch.int32, device=x.device) if want_tau else None,
                 torch.zeros(lead + (n_frames, n // 2 + 1), dtype=torch.float32, device=x.device) if want_cmnd else None)
     device = require_gpu(x.device)
-    lib = _lib.load()
     x2 = ingest(x.reshape(batch, x.shape[-1]), device, torch.float32)
     period = torch.empty((batch, n_frames), dtype=torch.float32, device=device)
     aper = torch.empty_like(period)
     tau = torch.empty((batch, n_frames), dtype=torch.int32, device=device) if want_tau else None
     cmnd = torch.empty((batch, n_frames, n // 2 + 1), dtype=torch.float32, device=device) if want_cmnd else None
-    stream = torch.cuda.current_stream(device)
     per_call = max(1, _MAX_BLOCKS // -(-n_frames // _WAVES))                         # items whose workgroups fit one call
     for b0 in range(0, batch, per_call):
         nb = min(per_call, batch - b0)
-        _lib.check(lib.specinv_yin(x2[b0:].data_ptr(), period[b0:].data_ptr(), aper[b0:].data_ptr(),
-                                   tau[b0:].data_ptr() if want_tau else None, cmnd[b0:].data_ptr() if want_cmnd else None, nb,
-                                   x2.shape[-1], n, h, int(bool(center)), tau_min, tau_max, threshold, _lib.F32,
-                                   stream.device.index, C.c_void_p(stream.cuda_stream)))
+        _lib.call_op("specinv_yin", (x2[b0:], period[b0:], aper[b0:], tau[b0:] if want_tau else None, cmnd[b0:] if want_cmnd else None,
+                                     nb, x2.shape[-1], n, h, int(bool(center)), tau_min, tau_max, threshold), False, device)
     return tuple(None if o is None else o.reshape(lead + tuple(o.shape[1:])).to(x.device) for o in (period, aper, tau, cmnd))
 
 
@@ -351,10 +341,8 @@ def _observe(xd, n, h, center, tau_min, tau_max, w, lam, q, n_bins, bps, sample_
     tables = _obs_tables(w, lam, n_ranks, xd.device)
     obs = torch.empty((batch, n_frames, n_bins), dtype=torch.float32, device=xd.device)
     vprob = torch.empty((batch, n_frames), dtype=torch.float32, device=xd.device)
-    stream = torch.cuda.current_stream(xd.device)
-    _lib.check(_lib.load().specinv_pyin_obs(cmnd.data_ptr(), tables.data_ptr(), obs.data_ptr(), vprob.data_ptr(), batch * n_frames, n,
-                                            tau_min, tau_max, len(w), n_ranks, n_bins, bps, float(sample_rate), float(fmin), q,
-                                            _lib.F32, stream.device.index, C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_pyin_obs", (cmnd, tables, obs, vprob, batch * n_frames, n, tau_min, tau_max, len(w), n_ranks, n_bins, bps,
+                                      float(sample_rate), float(fmin), q), False, xd.device)
     return obs, vprob
 
 
@@ -364,11 +352,8 @@ def _decode(obs, vprob, half, switch, ticks=None):
     tables = _decode_tables(n_bins, half, obs.device)
     backptr = torch.empty((batch, n_frames, 2 * n_bins), dtype=torch.int16, device=obs.device)
     states = torch.empty((batch, n_frames), dtype=torch.int32, device=obs.device)
-    stream = torch.cuda.current_stream(obs.device)
-    _lib.check(_lib.load().specinv_pyin_viterbi(obs.data_ptr(), vprob.data_ptr(), tables.data_ptr(), backptr.data_ptr(),
-                                                states.data_ptr(), None if ticks is None else ticks.data_ptr(), batch, n_frames,
-                                                n_bins, half, switch, _lib.F32, stream.device.index,
-                                                C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_pyin_viterbi", (obs, vprob, tables, backptr, states, ticks, batch, n_frames, n_bins, half, switch), False,
+                 obs.device)
     return states
 
 
@@ -471,7 +456,7 @@ def pyin(x, sample_rate, fmin, fmax, frame_length=2048, hop_length=None, n_thres
     lam, q = _checked_obs_params(boltzmann_parameter, no_trough_prob)
     switch = _checked_switch(switch_prob)
     half = _transition_half(sample_rate, h, bps, max_transition_rate)
-    if not isinstance(fill_na, numbers.Real) or isinstance(fill_na, bool):
+    if not is_real(fill_na):
         raise ValueError(f"fill_na must be a number, got {fill_na!r}")
     xd, lead, n_frames = _pyin_signal(x, "pyin", n, h, center)
     if xd is None:

@@ -17,13 +17,12 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import ingest, is_int
 from .plan import require_gpu
 
 __all__ = ["resample"]
@@ -34,7 +33,7 @@ _MAX_HALF_WIDTH = 1 << 30
 
 
 def _checked_int(value, name):
-    if isinstance(value, bool) or not isinstance(value, int):
+    if not is_int(value):
         raise ValueError(f"{name} must be an int, got {type(value).__name__}")
     if value < 1:
         raise ValueError(f"{name} must be >= 1, got {value}")
@@ -83,12 +82,8 @@ def resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     if x.numel() == 0 or n_out == 0:
         return x.new_zeros(x.shape[:-1] + (n_out,))
     device = require_gpu(x.device)
-    lib = _lib.load()
     dtype = _REAL[x.dtype]
     x2 = ingest(x.reshape(-1, n_in), device, dtype)
     out = torch.empty((x2.shape[0], n_out), dtype=dtype, device=device)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_resample(x2.data_ptr(), out.data_ptr(), x2.shape[0], n_in, n_out, o, n, width, rolloff,
-                                    _lib.F32 if dtype == torch.float32 else _lib.F64, stream.device.index,
-                                    C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_resample", (x2, out, x2.shape[0], n_in, n_out, o, n, width, rolloff), dtype != torch.float32, device)
     return out.reshape(x.shape[:-1] + (n_out,)).to(device=x.device, dtype=x.dtype)

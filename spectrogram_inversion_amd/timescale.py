@@ -31,7 +31,6 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 import math
 import numbers
@@ -98,16 +97,12 @@ def _pvoc_pghi(spec3, rate, n_out, lock_tol, return_parents, stft_kwargs):
     if spec3.shape[1] > _PGHI_MAX_FREQ:
         raise NotImplementedError(f"phase_lock='pghi': {spec3.shape[1]} bins are beyond the kernel's limit of {_PGHI_MAX_FREQ}")
     device = require_gpu(spec3.device)
-    lib = _lib.load()
     real = spec3.real.dtype
     s = ingest(spec3, device, spec3.dtype)
     out = torch.empty((s.shape[0], s.shape[1], n_out), dtype=s.dtype, device=device)
     parents = torch.empty(out.shape, dtype=torch.int8, device=device) if return_parents else None
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_pvoc_pghi(s.data_ptr(), out.data_ptr(), parents.data_ptr() if return_parents else None, s.shape[0],
-                                     s.shape[1], s.shape[2], n_out, args.n_fft, args.hop_length, rate, lock_tol,
-                                     _lib.F32 if real == torch.float32 else _lib.F64, stream.device.index,
-                                     C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_pvoc_pghi", (s, out, parents, s.shape[0], s.shape[1], s.shape[2], n_out, args.n_fft, args.hop_length, rate,
+                                       lock_tol), real != torch.float32, device)
     return out, parents
 
 

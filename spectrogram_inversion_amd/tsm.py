@@ -46,14 +46,13 @@ Not part of the reference's surface.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._ingest import ingest
+from ._ingest import ingest, is_int
 from .plan import require_gpu
 from .timescale import _METHODS, _checked_lock_tol, _checked_rate
 
@@ -65,7 +64,7 @@ _REAL = {torch.float16: torch.float32, torch.bfloat16: torch.float32, torch.floa
 
 
 def _int_in(value, name, lo, hi, what):
-    if isinstance(value, bool) or not isinstance(value, int):
+    if not is_int(value):
         raise ValueError(f"{name} must be an int, got {value!r}")
     if value < lo or value > hi:
         raise ValueError(f"{name} must be {what}, got {value}")
@@ -134,7 +133,6 @@ def _run(x, rate, n, hop, tol, window, length, return_lags, what):
         y = x.new_zeros(x.shape[:-1] + (n_out,))
         return (y, torch.zeros(x.shape[:-1] + (n_frames,), dtype=torch.int32, device=x.device)) if return_lags else y
     device = require_gpu(x.device)
-    lib = _lib.load()
     dtype = _REAL[x.dtype]
     x2 = ingest(x.reshape(-1, n_in), device, dtype)
     # (the default window is made on the CPU: the same bits on every device, and those a caller's own hann_window(N) has)
@@ -142,10 +140,8 @@ def _run(x, rate, n, hop, tol, window, length, return_lags, what):
     centres = torch.from_numpy(wsola_centres(n_frames, hop, rate)).to(device)
     y = torch.empty((x2.shape[0], n_out), dtype=dtype, device=device)
     lags = torch.empty((x2.shape[0], n_frames), dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device)
-    _lib.check(lib.specinv_wsola(x2.data_ptr(), centres.data_ptr(), w.data_ptr(), lags.data_ptr(), y.data_ptr(), x2.shape[0], n_in,
-                                 n_out, n_frames, n, hop, tol, _lib.F32 if dtype == torch.float32 else _lib.F64,
-                                 stream.device.index, C.c_void_p(stream.cuda_stream)))
+    _lib.call_op("specinv_wsola", (x2, centres, w, lags, y, x2.shape[0], n_in, n_out, n_frames, n, hop, tol), dtype != torch.float32,
+                 device)
     y = y.reshape(x.shape[:-1] + (n_out,)).to(device=x.device, dtype=x.dtype)
     if not return_lags:
         return y
@@ -203,7 +199,7 @@ def time_stretch_hpss(x, rate, n_fft=None, kernel_size=31, power=2.0, hpss_iter=
     rate = _checked_rate(rate)
     if method not in _METHODS:
         raise ValueError(f"method must be one of {', '.join(_METHODS)}, got {method!r}")
-    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
+    if not is_int(max_iter) or max_iter < 0:
         raise ValueError(f"max_iter must be an int >= 0, got {max_iter!r}")
     _checked_frame(perc_frame, perc_hop, "perc_frame", "perc_hop")
     if not kwargs.get("center", True):

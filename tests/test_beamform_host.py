@@ -183,6 +183,53 @@ def test_empty_input_needs_no_gpu():
     assert si.beamform_apply(_spec(2, 3, 0), torch.zeros(3, 2, dtype=torch.complex128)).shape == (3, 0)
 
 
+def test_entry_argument_errors_do_not_need_a_gpu():
+    """specinv_beamform's checks, in the header's order, on pointers that are never read"""
+    from spectrogram_inversion_amd import _lib, build
+    build.build_lib()
+    lib = _lib.load()
+    p = [0x1000 * (i + 1) for i in range(8)]       # spec, mask_target, mask_noise, weights_in, out, weights_out, scm_target, scm_noise
+
+    def call(ptrs, batch=1, channels=2, n_freq=5, n_frames=7, solution=0, ref=0, n_power=3, load=1e-7, mu=1.0, dtype=_lib.F32):
+        return lib.specinv_beamform(*ptrs, batch, channels, n_freq, n_frames, solution, ref, n_power, load, mu, dtype, 0, None)
+
+    def fails(code, word, ptrs, **kw):
+        assert call(ptrs, **kw) == code, (word, kw)
+        assert word in lib.specinv_last_error(), (word, kw, lib.specinv_last_error())
+
+    estimate = [p[0], p[1], p[2], None, p[4], p[5], p[6], p[7]]
+    apply = [p[0], None, None, p[3], p[4], None, None, None]
+    # the pointers and the mode rules (each with batch = 0 as well: a later check must not answer first)
+    for kw in ({}, {"batch": 0}):
+        fails(_lib.EINVAL, b"NULL spec", [None] + estimate[1:], **kw)
+        for i in (1, 2, 5, 6, 7):                                # weights_in with a mask, weights_out or a covariance
+            fails(_lib.EINVAL, b"with weights_in given nothing is estimated", apply[:i] + [p[i]] + apply[i + 1:], **kw)
+        fails(_lib.EINVAL, b"with weights_in given nothing is estimated", apply[:4] + [None] * 4, **kw)      # ... or without out
+        fails(_lib.EINVAL, b"no result is asked for", estimate[:4] + [None] * 4, **kw)
+        fails(_lib.EINVAL, b"weights need mask_target", [p[0], None, p[2], None, p[4], None, p[6], p[7]], **kw)
+        fails(_lib.EINVAL, b"weights need mask_target", [p[0], None, None, None, None, p[5], None, None], **kw)
+        fails(_lib.EINVAL, b"out must not alias spec", estimate[:4] + [p[0]] + estimate[5:], **kw)
+        fails(_lib.EINVAL, b"out must not alias weights_in", apply[:4] + [p[3]] + apply[5:], **kw)
+        fails(_lib.EINVAL, b"weights_out must not alias mask_target", estimate[:5] + [p[1]] + estimate[6:], **kw)
+        fails(_lib.EINVAL, b"scm_target must not alias out", estimate[:6] + [p[4], p[7]], **kw)
+        fails(_lib.EINVAL, b"scm_noise must not alias scm_target", estimate[:7] + [p[6]], **kw)
+    # the numbers, in the header's order; n_power_iter = 65 (the last check, EUNSUPPORTED) rides along and must not answer first
+    numbers = (({"batch": 0}, b"must be >= 1"), ({"channels": 0}, b"must be >= 1"), ({"n_freq": 0}, b"must be >= 1"),
+               ({"n_frames": 0}, b"must be >= 1"), ({"batch": 1 << 40, "n_freq": 1 << 20}, b"are too many"),
+               ({"solution": 3}, b"unknown solution 3"), ({"solution": -1}, b"unknown solution -1"),
+               ({"ref": -1}, b"ref_channel must be in [0, 2)"), ({"ref": 2}, b"ref_channel must be in [0, 2)"),
+               ({"load": -1.0}, b"diag_load and mu"), ({"load": float("nan")}, b"diag_load and mu"),
+               ({"mu": float("inf")}, b"diag_load and mu"), ({"mu": -1e-3}, b"diag_load and mu"), ({"dtype": 7}, b"bad dtype 7"))
+    for ptrs in (estimate, apply):
+        for kw, word in numbers:
+            fails(_lib.EINVAL, word, ptrs, **kw)
+            fails(_lib.EINVAL, word, ptrs, **{"n_power": 65, **kw})
+        fails(_lib.EINVAL, b"n_power_iter must be >= 1", ptrs, n_power=0)
+        fails(_lib.EUNSUPPORTED, b"channels must be <= 16", ptrs, channels=17)
+        fails(_lib.EUNSUPPORTED, b"channels must be <= 16", ptrs, channels=17, n_power=65)
+        fails(_lib.EUNSUPPORTED, b"n_power_iter must be <= 64", ptrs, n_power=65)
+
+
 # ------------------------------------------------------------------------------------------------ recorded figures
 
 def test_order_sensitivity_table():

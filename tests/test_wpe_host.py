@@ -161,6 +161,54 @@ def test_empty_input_needs_no_gpu():
     assert y.shape == (0, 2, 3, 8) and g.shape == (0, 3, 2, 2, 2) and g.dtype == torch.complex128 and lam.shape == (0, 3, 8)
 
 
+def test_entry_argument_errors_do_not_need_a_gpu():
+    """specinv_wpe's checks, in the header's order, on pointers that are never read"""
+    from spectrogram_inversion_amd import _lib, build
+    build.build_lib()
+    lib = _lib.load()
+    p = [0x1000 * (i + 1) for i in range(7)]       # spec, power, filt_in, out, filt_out, lam, scratch
+
+    def call(ptrs, batch=1, channels=2, n_freq=5, n_frames=7, taps=3, delay=2, n_iter=1, ctx=0, eps=1e-10, load=1e-10, dtype=_lib.F32):
+        return lib.specinv_wpe(*ptrs, batch, channels, n_freq, n_frames, taps, delay, n_iter, ctx, eps, load, dtype, 0, None)
+
+    def fails(code, word, ptrs, **kw):
+        assert call(ptrs, **kw) == code, (word, kw)
+        assert word in lib.specinv_last_error(), (word, kw, lib.specinv_last_error())
+
+    estimate = [p[0], p[1], None, p[3], p[4], p[5], p[6]]
+    apply = [p[0], None, p[2], p[3], None, None, None]
+    # the pointers and the mode rules (each with batch = 0 as well: a later check must not answer first)
+    for kw in ({}, {"batch": 0}):
+        fails(_lib.EINVAL, b"NULL spec or out", [None] + estimate[1:], **kw)
+        fails(_lib.EINVAL, b"NULL spec or out", apply[:3] + [None] + apply[4:], **kw)
+        for i in (1, 4, 5):                                      # filt_in with power, filt_out or lam
+            fails(_lib.EINVAL, b"with filt_in given nothing is estimated", apply[:i] + [p[i]] + apply[i + 1:], **kw)
+        fails(_lib.EINVAL, b"lam is NULL", estimate[:5] + [None, p[6]], **kw)
+        fails(_lib.EINVAL, b"psd_context > 0 needs the scratch", estimate[:6] + [None], ctx=1, **kw)
+        fails(_lib.EINVAL, b"out must not alias spec", estimate[:3] + [p[0]] + estimate[4:], **kw)
+        fails(_lib.EINVAL, b"out must not alias filt_in", apply[:3] + [p[2]] + apply[4:], **kw)
+        fails(_lib.EINVAL, b"filt_out must not alias power", estimate[:4] + [p[1]] + estimate[5:], **kw)
+        fails(_lib.EINVAL, b"lam must not alias filt_out", estimate[:5] + [p[4], p[6]], **kw)
+        fails(_lib.EINVAL, b"scratch must not alias out", estimate[:6] + [p[3]], **kw)
+    # the numbers, in the header's order; n_iter = 101 (the last check, EUNSUPPORTED) rides along and must not answer first
+    numbers = (({"batch": 0}, b"must be >= 1"), ({"channels": 0}, b"must be >= 1"), ({"n_freq": 0}, b"must be >= 1"),
+               ({"n_frames": 0}, b"must be >= 1"), ({"batch": 1 << 40, "n_freq": 1 << 20}, b"are too many"),
+               ({"taps": 0}, b"taps must be >= 1"), ({"delay": 0}, b"delay must be >= 1"),
+               ({"ctx": -1}, b"n_iter and psd_context must be >= 0"), ({"eps": -1.0}, b"eps and diag_load"),
+               ({"eps": float("nan")}, b"eps and diag_load"), ({"load": float("inf")}, b"eps and diag_load"),
+               ({"load": -1e-3}, b"eps and diag_load"), ({"dtype": 7}, b"bad dtype 7"))
+    for ptrs in (estimate, apply):
+        for kw, word in numbers:
+            fails(_lib.EINVAL, word, ptrs, **kw)
+            fails(_lib.EINVAL, word, ptrs, **{"n_iter": 101, **kw})
+        fails(_lib.EINVAL, b"n_iter and psd_context must be >= 0", ptrs, n_iter=-1)
+        for kw in ({"channels": 65, "taps": 1}, {"channels": 1, "taps": 65}, {"channels": 8, "taps": 9}):
+            fails(_lib.EUNSUPPORTED, b"channels x taps must be <= 64", ptrs, **kw)
+            fails(_lib.EUNSUPPORTED, b"channels x taps must be <= 64", ptrs, n_iter=101, **kw)
+        fails(_lib.EUNSUPPORTED, b"n_iter must be <= 100", ptrs, n_iter=101)
+        fails(_lib.EUNSUPPORTED, b"psd_context <= 64", ptrs, ctx=65)
+
+
 # ------------------------------------------------------------------------------------------------ recorded figures
 
 def _cond(name):
